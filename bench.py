@@ -1,10 +1,15 @@
-"""Benchmark: preconditioner applies per second on the multiphase-Stokes system on MI355X, with the roofline
+"""Benchmark: preconditioner applies per second on the multiphase-Stokes system on MI355X; with --full the roofline
 of the dominant kernel and the CPU oracle timed beside it.
 
 One step = one application of the approximate-commutator block preconditioner (solve.py:257-277,
 ``mpbp_schur_apply``) to a resident random vector of 5 n^2 doubles.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid n] [--weak] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--grid n] [--weak] ...
+
+A plain run sets up, settles the clocks, runs the W warmup and the K timed applies, writes the last apply's output
+(--dump-outputs) and prints the headline line.  --full adds every other section (the A u SpMV and F-solve rooflines,
+the host-buffer matvec, the multigrid apply, the CPU baselines, the FGMRES solves; N > 1: the eager rate, the one-GPU
+bit-exact check and the distributed solve); the headline's meaning is the same in both.
 
 N = 1: BASELINE configs[2], the 1024^2 grid on one GPU.  N > 1: BASELINE configs[4], the 2048^2 grid row-
 partitioned over N ranks (one per GPU, RCCL point-to-point halos).  `python bench.py --gpus N` launches the N
@@ -28,6 +33,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0    # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level parameters)
 _KEEP_ALIVE = []         # objects whose lifetime must span the run (an installed kernel_options scope)
+SETTLE_SECONDS = 0.2     # a plain run's eager applies before the warmup (the clocks ramp over ~35 ms of load)
+DUMP_MAX_BYTES = 60 * 10 ** 6   # --dump-outputs: all files of one run together stay under 64 MB
 MG_KW = {}               # --mg-coarsest: InnerSolver keyword arguments of every multigrid inner solve the run builds
 
 
@@ -114,8 +121,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks (one per GPU); default WORLD_SIZE or 1.  Without WORLD_SIZE, N > 1 launches N ranks")
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed applies (at least 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every section beside the headline: the A u SpMV roofline, the F solves' HIP-event "
+                         "roofline, the host-buffer matvec, the multigrid apply, the CPU baselines and the FGMRES solves "
+                         "(N > 1: the eager rate, the one-GPU check and the distributed solve).  A plain run sets up, "
+                         "settles the clocks, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the output vector of the last timed apply to DIR/apply_out.npy "
+                         "(float64; N > 1: DIR/apply_out_rank<r>.npy, each rank's rows; above 60 MB in all a fixed seeded "
+                         "sample of the entries, in index order)")
     ap.add_argument("--grid", "--grid-n", dest="n", type=int, default=None,
                     help="global grid size n (n x n cells); default 1024 at N = 1 (configs[2]), 2048 at N > 1 "
                          "(configs[4])")
@@ -204,6 +220,10 @@ def main():
                     help="also write the full record (every note and timing description) to PATH; stdout keeps the "
                          "compact line")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:   # a plain run measures the headline alone: every other section is off
+        args.no_spmv = args.no_mg = args.no_solve = args.no_cpu_baseline = args.no_check = True
 
     # --gpus N > 1 without a launcher: start the N ranks as a child process BEFORE anything touches the GPU
     # (torch is not even imported yet) and exit with its status; never re-exec this process
@@ -315,7 +335,8 @@ def main():
     # host-staged collectives between kernels, which a graph cannot hold).  The timed loop
     # records no events; the F-sweep durations for the roofline come from HIP events that
     # mpbp_schur_apply records around every F sweep on the apply stream, in an eager pass of the same K
-    # applies.  That pass and (N = 1) the A u SpMV section run BEFORE the W warmup applies and the timed loop:
+    # applies (--full; a plain run launches eager applies without events in its place).  That pass and (N = 1, --full)
+    # the A u SpMV section run BEFORE the W warmup applies and the timed loop:
     # the GPU then enters the timed loop at its sustained clocks, as inside a solver loop (with nothing before the
     # 5 warmup applies the 20 timed ones read ~9 % lower: the clocks ramp over ~35 ms of load,
     # profiles/r03w_warmup_sc1_ab.jsonl).
@@ -323,7 +344,7 @@ def main():
     # N > 1: the eager applies/s first, before any capture is attempted -- a capture that fails (or never returns) on a
     # node where the RCCL point-to-point path was never run still leaves this number
     eager_rate = None
-    if world > 1:
+    if world > 1 and args.full:
         dte = timed_loop(lambda: pc.apply(v, out), args.steps, args.warmup, world, dist, torch)
         eager_rate = args.steps / dte * (n * n / float(1024 * 1024))
     graph, graph_note = None, None
@@ -346,13 +367,26 @@ def main():
     if A is not None and not args.no_spmv:
         spmv = spmv_bench(A, gen)
         _progress(rank, "spmv section done")
-    pc.enable_profiling(max(1, args.steps * sweeps_per_apply))
-    pc.reset_profiling()
-    for _ in range(args.steps):
-        pc.apply(v, out)
-    torch.cuda.synchronize()
-    sweep_ms = pc.profiled_ms()
-    pc.disable_profiling()
+    sweep_ms = None
+    if args.full:
+        pc.enable_profiling(max(1, args.steps * sweeps_per_apply))
+        pc.reset_profiling()
+        for _ in range(args.steps):
+            pc.apply(v, out)
+        torch.cuda.synchronize()
+        sweep_ms = pc.profiled_ms()
+        pc.disable_profiling()
+    else:
+        # a plain run has no untimed sections to ramp the clocks: eager applies of the timed path (no events) for
+        # SETTLE_SECONDS of load, so the W warmup applies start from the sustained clocks as they do under --full
+        # (N > 1: the same K applies on every rank as the profiling pass, the halo exchanges pair up by count)
+        t0 = time.perf_counter()
+        while True:
+            for _ in range(args.steps):
+                pc.apply(v, out)
+            torch.cuda.synchronize()
+            if world > 1 or time.perf_counter() - t0 >= SETTLE_SECONDS:
+                break
     for _ in range(args.warmup):
         graph.replay() if graph is not None else pc.apply(v, out)
     torch.cuda.synchronize()
@@ -370,6 +404,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     launch = "hipgraph" if graph is not None else "eager"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
 
     # N > 1: every rank compares its rows of the partitioned apply with the one-GPU apply of the global
     # system (built on its own GPU from the same operators), bit for bit; plus an order-free checksum of
@@ -399,7 +435,7 @@ def main():
     f_solve = (args.f_solve is None or args.f_solve != 0) and (not partitioned or bool(getattr(pc, "ca", False))) and \
         ((sf == 4 and n >= 72) or (sf == 3 and n >= 70))
     per_apply, kname = sweep_bytes(pc, args.layout, kf, sf, fused_init, f_tile, f_solve)
-    sbytes, avg_sweep_s, n_timed = roofline_of(per_apply, sweep_ms, 1)
+    sbytes, avg_sweep_s, n_timed = roofline_of(per_apply, sweep_ms, 1)   # (a plain run: no events, nan and 0)
     achieved = sbytes / avg_sweep_s / 1e9
     gbytes, g_s, g_timed = roofline_of(per_apply, sweep_ms, 2)
 
@@ -423,7 +459,7 @@ def main():
     # the LinearOperator boundary with host buffers (solve.py:281: pyamg on the host hands M a numpy
     # vector): H2D of v + apply + D2H of the result per call.  Reported beside `value`, never as it.
     host_io = None
-    if rank == 0 and not partitioned:
+    if rank == 0 and not partitioned and args.full:
         vh = v.cpu().numpy()
         pc.matvec(vh)
         torch.cuda.synchronize()
@@ -539,6 +575,10 @@ def main():
             "time_to_solution": time_to_solution(solve, n),
             "cpu_baseline": cpu,
         }
+        if not args.full:   # no HIP-event pass: the F solves' rooflines are --full's
+            line["roofline"] = line["roofline_second_f_solve"] = None
+            line["config"]["before_timed_loop"] = ("K eager applies" if world > 1 else
+                                                   f"eager applies for {SETTLE_SECONDS} s") + ", then W warmup applies"
         if args.detail_json:   # the verbose record (every note and timing description) beside the printed line
             with open(args.detail_json, "w") as f:
                 json.dump(line, f, indent=1)
@@ -657,6 +697,19 @@ def _progress(rank, msg):
     the one JSON line."""
     if rank == 0:
         print(f"[bench] {msg}", file=sys.stderr, flush=True)
+
+
+def dump_outputs(path, out, rank, world):
+    """--dump-outputs: the output vector of the last timed apply (this rank's rows) as float64 .npy.  Within
+    DUMP_MAX_BYTES over all ranks it is written whole; a larger one as a fixed sample of its entries (numpy seed 0,
+    without replacement, in index order), the same entries on every run of the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    a = out.detach().cpu().numpy().astype(np.float64, copy=False)
+    keep = DUMP_MAX_BYTES // world // a.itemsize
+    if a.size > keep:
+        a = a[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+    np.save(os.path.join(path, "apply_out.npy" if world == 1 else f"apply_out_rank{rank}.npy"), a)
 
 
 def timed_loop(fn, steps, warmup, world, dist, torch):

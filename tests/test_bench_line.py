@@ -3,6 +3,8 @@
 import json
 import os
 
+import pytest
+
 import bench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,3 +43,35 @@ def test_compact_line_without_optional_sections():
     line = bench.compact_line(full)
     assert line["cpu_baseline"] is None and line["vs_baseline"] is None   # contract keys stay, even when null
     assert "roofline_csr_spmv" not in line and "mg_apply" not in line
+
+
+def test_compact_line_of_a_plain_run():
+    """Without --full the record has no section beside the headline: the contract's keys stay (null where unmeasured)."""
+    full = _full_record()
+    for k in ("roofline", "roofline_second_f_solve", "spmv_A", "roofline_csr_spmv", "mg_apply", "solve_level",
+              "time_to_solution", "host_buffer_matvec", "cpu_baseline"):
+        full[k] = None
+    line = bench.compact_line(full)
+    for k in CONTRACT:
+        assert k in line, k
+    assert line["roofline"] is None and line["cpu_baseline"] is None
+    assert line["value"] == full["value"] and line["ms_per_step"] == full["ms_per_step"]
+    assert set(line) == set(CONTRACT), set(line) ^ set(CONTRACT)
+    json.dumps(line, allow_nan=False)
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: a float64 .npy of the output vector; above the size limit the same seeded sample every time."""
+    import numpy as np
+    torch = pytest.importorskip("torch")
+    out = torch.arange(1000, dtype=torch.float64) * 0.5
+    bench.dump_outputs(str(tmp_path / "a"), out, 0, 1)
+    a = np.load(tmp_path / "a" / "apply_out.npy")
+    assert a.dtype == np.float64 and np.array_equal(a, out.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 200)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), out, 1, 2)   # two ranks share the limit: 100 entries each
+    b, c = (np.load(tmp_path / d / "apply_out_rank1.npy") for d in ("b", "c"))
+    assert b.shape == (100,) and np.array_equal(b, c)
+    idx = (b * 2).astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(out.numpy()[idx], b)

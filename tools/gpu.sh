@@ -7,7 +7,7 @@
 # Steps:
 #   tests        pytest -m gpu (all GPU parity tests)          smoke     __graft_entry__.smoke()
 #   tests:F1,F2  pytest -m gpu of the named test files / node ids only
-#   bench        bench.py, N = 1 (the driver's command)        bench_csr bench.py --layout csr
+#   bench        bench.py --full, N = 1 (every section)        bench_csr bench.py --full --layout csr
 #   bench:ARGS   bench.py ARGS ('+' for spaces; MPBP_BENCH_BACKEND etc. from the environment), appended to bench_args.log
 #   rows2_gloo   bench.py --gpus 2 --grid 512 over gloo on one GPU (the N > 1 path; launcher inside bench.py)
 #   gloo:N       bench.py --gpus N (configs[4]'s 2048^2) over gloo on one GPU: the N > 1 line's sections rehearsed
@@ -50,25 +50,25 @@ step() {
     tests:*) timeout -k 10 900 python -u -m pytest $(echo "${s#tests:}" | tr , ' ') -x -q --timeout 240 \
                --timeout-method thread -m gpu > "$OUT/pytest_part.log" 2>&1 ;;
     smoke) timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 ;;
-    bench) timeout -k 10 300 python bench.py --steps 20 --warmup 5 > "$OUT/bench.log" 2>&1 ;;
+    bench) timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench.log" 2>&1 ;;
     bench:*) local A=$(echo "${s#bench:}" | tr + ' ')   # bench.py with extra arguments ('+' for spaces)
           timeout -k 10 400 python bench.py $A >> "$OUT/bench_args.log" 2>&1 ;;
-    bench_csr) timeout -k 10 300 python bench.py --steps 20 --warmup 5 --layout csr --no-cpu-baseline \
+    bench_csr) timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --layout csr --no-cpu-baseline \
                  > "$OUT/bench_csr.log" 2>&1 ;;
-    rows2_gloo) MPBP_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --steps 5 --warmup 2 --grid 512 \
+    rows2_gloo) MPBP_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 --steps 5 --warmup 2 --grid 512 \
                   > "$OUT/rows2_gloo.log" 2>&1 ;;
-    gloo:*) MPBP_BENCH_BACKEND=gloo timeout -k 10 900 python bench.py --gpus ${s#gloo:} --steps 5 --warmup 2 \
+    gloo:*) MPBP_BENCH_BACKEND=gloo timeout -k 10 900 python bench.py --full --gpus ${s#gloo:} --steps 5 --warmup 2 \
               > "$OUT/gloo_${s#gloo:}.log" 2>&1 ;;
-    selfhalo) timeout -k 10 300 python bench.py --self-halo --steps 20 --warmup 5 --no-cpu-baseline --no-spmv \
+    selfhalo) timeout -k 10 300 python bench.py --full --self-halo --steps 20 --warmup 5 --no-cpu-baseline --no-spmv \
                 > "$OUT/selfhalo.log" 2>&1 ;;
     probe) timeout -k 10 120 python -u tools/capture_probe.py 256 1024 > "$OUT/probe.log" 2>&1 ;;
     probe:*) timeout -k 10 120 python -u tools/capture_probe.py $(echo "${s#probe:}" | tr , ' ') \
                > "$OUT/probe_${s#probe:}_${MPBP_HALO_CAPTURED_DESTROY:-leak}.log" 2>&1 ;;
     prof) prof prof 300 --kernel-trace --stats --output-format csv -d "$ROOTD/$OUT/prof" -o run -- \
-            python "$ROOTD/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-solve $BENCH_ARGS &&
+            python "$ROOTD/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-solve $BENCH_ARGS &&
           python tools/prof_summary.py "$OUT/prof/run_kernel_trace.csv" > "$OUT/prof_summary.md" 2>&1 ;;
     profmg) prof prof_mg 300 --kernel-trace --stats --output-format csv -d "$ROOTD/$OUT/prof_mg" -o run -- \
-              python "$ROOTD/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-solve --no-mg --no-spmv \
+              python "$ROOTD/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-solve --no-mg --no-spmv \
               --inner-f mg:1 --inner-p mg:1 &&
             python tools/prof_summary.py "$OUT/prof_mg/run_kernel_trace.csv" > "$OUT/prof_mg_summary.md" 2>&1 ;;
     profsolve) prof prof_solve 300 --kernel-trace --stats --output-format csv -d "$ROOTD/$OUT/prof_solve" -o run -- \
@@ -76,7 +76,7 @@ step() {
                python tools/prof_summary.py "$OUT/prof_solve/run_kernel_trace.csv" > "$OUT/prof_solve_summary.md" 2>&1 ;;
     pmc) for C in FETCH_SIZE WRITE_SIZE; do
            prof "pmc_apply_$C" 150 --pmc $C --output-format csv -d "$ROOTD/$OUT/pmc_apply_$C" -o pmc -- \
-             python "$ROOTD/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-spmv --no-graph --no-solve || return 1
+             python "$ROOTD/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-spmv --no-graph --no-solve || return 1
            prof "pmc_spmv_$C" 120 --pmc $C --output-format csv -d "$ROOTD/$OUT/pmc_spmv_$C" -o pmc -- \
              python "$ROOTD/tools/spmv_ab.py" --reps 10 || return 1
          done ;;
@@ -100,7 +100,7 @@ step() {
             [ "$N" != "$V" ] && A=$(echo "${V#*@}" | tr + ' ')
             local L=mp-block-preconditioners_amd/lib/variants/libmpbp_$N.so
             [ "$N" = base ] && L=
-            MPBP_LIB=$L timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-spmv $A \
+            MPBP_LIB=$L timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-spmv $A \
               $BENCH_ARGS >> "$OUT/ab_bench_$N$(echo "$A" | tr -d ' -').log" 2>&1 || return 1
           done ;;
     spmv:*) local V
@@ -109,7 +109,7 @@ step() {
             [ "$V" = base ] && L=
             MPBP_LIB=$L timeout -k 10 120 python tools/spmv_ab.py >> "$OUT/spmv_$V.log" 2>&1 || return 1
           done ;;
-    sqapply|sqmg) local B="$ROOTD/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-spmv --no-graph"
+    sqapply|sqmg) local B="$ROOTD/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-spmv --no-graph"
           [ "$s" = sqmg ] && B="$B --no-mg --no-solve --inner-f mg:1 --inner-p mg:1 $SQMG_ARGS"
           prof sq1_apply 150 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY \
             SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU --output-format csv -d "$ROOTD/$OUT/sq1_apply" \

@@ -331,6 +331,21 @@ int mpbp_exclusive_scan(const int32_t* row_nnz, int32_t* row_ptr, int64_t n, int
 int mpbp_spgemm_count(const mpbp_csr* A, const mpbp_csr* B, int32_t* row_nnz, void* stream);
 int mpbp_spgemm_fill(const mpbp_csr* A, const mpbp_csr* B, double alpha, const int32_t* row_ptr,
                      int32_t* col_idx, double* val, void* stream);
+/* Values-only products into a pattern that is already known (a time step's new coefficients on the same grid): only
+ * C->val is written, C's row_ptr / col_idx are read.  One wavefront per output row, lane t owning the row's entry t;
+ * every entry receives its products in mpbp_spgemm_fill's order, so the values are that builder's bit for bit (composed
+ * twice for the triple, whose inner product is never stored).
+ *   mpbp_spgemm_refill   C = alpha A B
+ *   mpbp_triple_refill   assoc MPBP_ASSOC_RIGHT: C = alpha_outer X (alpha_inner Y Z)   (a Galerkin R (A P))
+ *                        assoc MPBP_ASSOC_LEFT:  C = alpha_outer (alpha_inner X Y) Z   (Gt_F_G = ((-D) F) G)
+ * Errors (nothing is read or written out of bounds; C->val is then partly written): MPBP_ERR_OVERFLOW for an output or
+ * inner row wider than 64, MPBP_ERR_PATTERN for a product whose column C's row lacks, MPBP_ERR_ARG for mismatched
+ * shapes or an index outside its array.  Setup: synchronises the stream. */
+#define MPBP_ASSOC_LEFT 0
+#define MPBP_ASSOC_RIGHT 1
+int mpbp_spgemm_refill(const mpbp_csr* A, const mpbp_csr* B, double alpha, const mpbp_csr* C, void* stream);
+int mpbp_triple_refill(const mpbp_csr* X, const mpbp_csr* Y, const mpbp_csr* Z, int32_t assoc, double alpha_inner,
+                       double alpha_outer, const mpbp_csr* C, void* stream);
 
 /* ---- Gt_F_G in the 13-point diamond layout ---------------------------------------------------- */
 /* Gt_F_G = ((-D) F) G (solve.py:246-249) couples each pressure cell with the 13 cells |dr| + |dc| <= 2 (n >= 5).

@@ -17,6 +17,7 @@ OK, ERR_ARG = 0, -1                    # mpbp.h return codes (MPBP_OK, MPBP_ERR_
 SPMV_FAST = 0x100                     # mpbp_f_stencil_spmv: tolerance-mode F rows
 NUMERICS_EXACT, NUMERICS_FAST = 0, 1  # mpbp_schur_plan.f_numerics
 INNER_JACOBI, INNER_CHEBYSHEV, INNER_MG = 0, 1, 2
+ASSOC_LEFT, ASSOC_RIGHT = 0, 1        # mpbp_triple_refill: (X Y) Z or X (Y Z)
 MG_CELL, MG_NODE = 0, 1
 MG_P, MG_R = 0, 1
 HALO_BEGIN, HALO_END = 0, 1
@@ -178,6 +179,9 @@ _SIGNATURES = {
     "mpbp_exclusive_scan": ([_P, _P, c_int64, POINTER(c_int64), _P], c_int),
     "mpbp_spgemm_count": ([POINTER(Csr), POINTER(Csr), _P, _P], c_int),
     "mpbp_spgemm_fill": ([POINTER(Csr), POINTER(Csr), c_double, _P, _P, _P, _P], c_int),
+    "mpbp_spgemm_refill": ([POINTER(Csr), POINTER(Csr), c_double, POINTER(Csr), _P], c_int),
+    "mpbp_triple_refill": ([POINTER(Csr), POINTER(Csr), POINTER(Csr), c_int32, c_double, c_double, POINTER(Csr), _P],
+                           c_int),
     "mpbp_plan_row_blocks": ([_P, c_int32, c_int32, _P, c_int64], c_int64),
     "mpbp_csr_diag": ([POINTER(Csr), c_int32, _P, POINTER(c_int32), _P], c_int),
     "mpbp_gershgorin": ([POINTER(Csr), _P, POINTER(c_double), _P], c_int),

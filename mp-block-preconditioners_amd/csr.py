@@ -7,7 +7,9 @@ on the device; every SpMV-shaped kernel walks them.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import time
 
 import numpy as np
 import torch
@@ -222,11 +224,20 @@ class DeviceSELL:
                                    ptr(col), stream_handle()))
         return cls(A, slices, int(need), row_len, val, col, int(pr.value))
 
+    def refill(self):
+        """The CSR's current values copied into the existing slices (same pattern: mpbp_sell_fill again, no planning,
+        no allocation).  On the copy itself, not on a sub() view."""
+        if getattr(self, "_view", False):
+            raise ValueError("refill the SELL copy itself, not a sub() view of it")
+        check(lib().mpbp_sell_fill(ctypes.byref(self.csr.cstruct()), ptr(self.slices), int(self.nslices),
+                                   ptr(self.row_len), ptr(self.val), ptr(self.col), stream_handle()))
+
     def sub(self, first: int, count: int):
         """The slices [first, first+count) as their own SELL view (shares storage)."""
         view = object.__new__(DeviceSELL)
         view.__dict__.update(self.__dict__)
         view.nslices = count
+        view._view = True
         view._cs = _lib.Sell(self.shape[0], self.shape[1], count, 0,
                              self.slices.data_ptr() + 16 * first if count else None, self.row_len.data_ptr(),
                              self.val.data_ptr(), self.col.data_ptr())
@@ -289,6 +300,22 @@ def wave_table(rp: np.ndarray, pairs: np.ndarray) -> np.ndarray:
             flags[idx] |= np.where(ok, L0, 0) << (8 * w)
     t[:, 7] = flags
     return t.astype(np.int32).reshape(-1)
+
+
+@contextlib.contextmanager
+def timed_phase(timings: dict | None, name: str):
+    """Adds the enclosed block's seconds to timings[name], the device synchronised before and after (the refresh
+    methods' per-phase split, tools/refresh_timing.py); timings None: nothing is timed or synchronised."""
+    if timings is None:
+        yield
+        return
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    try:
+        yield
+    finally:
+        torch.cuda.synchronize()
+        timings[name] = timings.get(name, 0.0) + time.perf_counter() - t0
 
 
 def csr_from_row_nnz(row_nnz: torch.Tensor, shape, device):

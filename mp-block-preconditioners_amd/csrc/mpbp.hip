@@ -521,6 +521,205 @@ __global__ void k_spgemm_fill(Csr A, Csr B, int32_t nrows, double alpha, const i
     }
 }
 
+// ------------------------------------------------ values-only products into a known pattern ----
+// One wavefront per output row, lane t owning the row's entry t (its column read from C.col_idx): every product of the
+// row is broadcast to the wave and the one lane whose column matches adds it, so each entry sees its products in
+// spgemm_row's (A row order, B row order) traversal and holds spgemm_row's bits.  A triple product's inner row is
+// built the same way into the lanes (first-touch order), scaled once and handed on through cross-lane reads -- it never
+// reaches memory.  No atomics on values, no private arrays, no scratch, no LDS allocation.
+struct RCsr {
+    const int32_t* rp;
+    const int32_t* ci;
+    const double* va;
+    int32_t nrows, ncols;
+    int64_t nnz;
+};
+
+constexpr int kRefillLong = 1;      // an output or inner row holds more than kSpgemmMaxW entries
+constexpr int kRefillMissing = 2;   // a product's column is not in C's row
+constexpr int kRefillIndex = 4;     // a row extent or column index outside its array
+
+// lane `src` (wave-uniform) of v
+__device__ inline int32_t lane_get(int32_t v, int src) { return __builtin_amdgcn_readlane(v, src); }
+__device__ inline double lane_get(double v, int src) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src),
+                            __builtin_amdgcn_readlane(__double2loint(v), src));
+}
+
+// [a, b) of row r (wave-uniform), false when it does not lie inside the entry arrays
+__device__ inline bool row_extent(const RCsr& M, int32_t r, int32_t& a, int32_t& b) {
+    a = M.rp[r];
+    b = M.rp[r + 1];
+    return a >= 0 && a <= b && (int64_t)b <= M.nnz;
+}
+
+// The wave's row: lane t < m holds entry t (col, val; hit: it has received a product).  m is wave-uniform.
+struct WaveRow {
+    int32_t col;
+    double val;
+    bool hit;
+    int m;
+};
+
+// One product (j, v), both wave-uniform.  APPEND: an unseen column becomes entry m (first-touch order, spgemm_row);
+// otherwise the pattern is fixed and an unseen column is an error.
+template <bool APPEND>
+__device__ inline void wave_feed(WaveRow& w, int lane, int32_t j, double v, int& err) {
+    const bool mine = lane < w.m && w.col == j;
+    if (__builtin_amdgcn_ballot_w64(mine)) {
+        if (mine) {
+            w.val = w.hit ? w.val + v : v;   // the first product is stored, later ones added (spgemm_row)
+            w.hit = true;
+        }
+    } else if (APPEND) {
+        if (w.m == kSpgemmMaxW) { err |= kRefillLong; return; }
+        if (lane == w.m) { w.col = j; w.val = v; w.hit = true; }
+        ++w.m;
+    } else {
+        err |= kRefillMissing;
+    }
+}
+
+__device__ inline int64_t lane_get(int64_t v, int src) {
+    return ((int64_t)__builtin_amdgcn_readlane((int32_t)(v >> 32), src) << 32) |
+           (uint32_t)__builtin_amdgcn_readlane((int32_t)v, src);
+}
+
+// inclusive prefix sum over the wave's lanes
+__device__ inline int64_t wave_scan(int64_t v, int lane) {
+    for (int d = 1; d < 64; d <<= 1) {
+        const int64_t u = __shfl_up(v, d, 64);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
+
+// lane t's value sent to lane dst (a permutation of the lanes)
+__device__ inline int32_t lane_push(int32_t v, int dst) { return __builtin_amdgcn_ds_permute(dst << 2, v); }
+__device__ inline double lane_push(double v, int dst) {
+    return __hiloint2double(lane_push(__double2hiint(v), dst), lane_push(__double2loint(v), dst));
+}
+
+// Feeds a_i * (row k_i of B) for the entries i < n the lanes hold (lane i: k, a), in entry order, each row in B's
+// order: spgemm_row's traversal of one A row.  The rows' extents, then their entries 64 at a time, are loaded one per
+// lane and the products formed there, so no row costs a dependent memory round trip of its own; only the accumulation
+// walks the products one by one.
+template <bool APPEND>
+__device__ inline void wave_feed_rows(WaveRow& w, int lane, int n, int32_t k, double a, const RCsr& B, int& err) {
+    int32_t b0 = 0, len = 0;
+    bool bad = false;
+    if (lane < n) {
+        bad = k < 0 || k >= B.nrows;
+        if (!bad) {
+            b0 = B.rp[k];
+            const int32_t b1 = B.rp[k + 1];
+            bad = b0 < 0 || b0 > b1 || (int64_t)b1 > B.nnz;
+            if (!bad) len = b1 - b0;
+        }
+    }
+    if (__builtin_amdgcn_ballot_w64(bad)) { err |= kRefillIndex; return; }
+    const int64_t incl = wave_scan(len, lane), excl = incl - len;   // products before / through entry `lane`
+    const int64_t total = lane_get(incl, 63);
+    int cur = 0;   // the first entry with products at or after `base`
+    for (int64_t base = 0; base < total; base += 64) {
+        const int64_t p = base + lane;   // this lane's product of the round
+        while (cur < n && lane_get(incl, cur) <= base) ++cur;
+        int own = -1;
+        for (int i = cur; i < n && lane_get(excl, i) < base + 64; ++i)
+            if (p >= lane_get(excl, i) && p < lane_get(incl, i)) own = i;
+        const int src = own < 0 ? 0 : own;
+        const int64_t at = (int64_t)__shfl(b0, src, 64) + (p - __shfl(excl, src, 64));
+        const double aa = __shfl(a, src, 64);
+        int32_t j = 0;
+        double v = 0.0;
+        if (own >= 0) { j = B.ci[at]; v = aa * B.va[at]; }
+        const int cnt = (int)min((int64_t)64, total - base);
+        for (int q = 0; q < cnt; ++q) wave_feed<APPEND>(w, lane, lane_get(j, q), lane_get(v, q), err);
+    }
+}
+
+// row r of A B in spgemm_row's traversal order
+template <bool APPEND>
+__device__ inline void wave_feed_product(WaveRow& w, int lane, const RCsr& A, const RCsr& B, int32_t r, int& err) {
+    int32_t a0, a1;
+    if (r < 0 || r >= A.nrows || !row_extent(A, r, a0, a1)) { err |= kRefillIndex; return; }
+    for (int64_t ca = a0; ca < a1; ca += 64) {
+        const int na = (int)min((int64_t)64, a1 - ca);
+        int32_t ak = 0;
+        double av = 0.0;
+        if (lane < na) { ak = A.ci[ca + lane]; av = A.va[ca + lane]; }
+        wave_feed_rows<APPEND>(w, lane, na, ak, av, B, err);
+    }
+}
+
+// lane t's rank among the row's columns (they are distinct): entry `rank` of the sorted row; lanes past the row keep
+// their own index, so the ranks are a permutation of the lanes
+__device__ inline int wave_rank(const WaveRow& w, int lane) {
+    int rank = 0;
+    for (int u = 0; u < w.m; ++u) rank += lane_get(w.col, u) < w.col ? 1 : 0;
+    return lane < w.m ? rank : lane;
+}
+
+constexpr int kRefillPair = 0, kRefillLeft = 1, kRefillRight = 2;
+
+// MODE pair:  C = alpha_outer X Y                    (Z unused)
+//      left:  C = alpha_outer (alpha_inner X Y) Z    -- inner row r once per output row, consumed in sorted-column
+//             order (the order spgemm_fill stored it in)
+//      right: C = alpha_outer X (alpha_inner Y Z)    -- inner row k per entry (r, k) of X; its columns are distinct,
+//             so each goes to another output entry and their order within the row reaches no sum
+template <int MODE>
+__global__ void __launch_bounds__(kBlock) k_refill(RCsr X, RCsr Y, RCsr Z, double alpha_inner, double alpha_outer,
+                                                   RCsr C, double* cva, int* errs) {
+    const int lane = threadIdx.x & 63;
+    const int32_t r = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);   // wave-uniform
+    if (r >= C.nrows) return;
+    int err = 0;
+    int32_t c0, c1;
+    if (!row_extent(C, r, c0, c1)) err |= kRefillIndex;
+    else if (c1 - c0 > kSpgemmMaxW) err |= kRefillLong;
+    if (!err) {
+        WaveRow w{0, 0.0, false, c1 - c0};
+        if (lane < w.m) w.col = C.ci[c0 + lane];
+        if (MODE == kRefillPair) {
+            wave_feed_product<false>(w, lane, X, Y, r, err);
+        } else if (MODE == kRefillLeft) {
+            WaveRow t{0, 0.0, false, 0};
+            wave_feed_product<true>(t, lane, X, Y, r, err);
+            const int rank = wave_rank(t, lane);
+            wave_feed_rows<false>(w, lane, t.m, lane_push(t.col, rank), lane_push(alpha_inner * t.val, rank), Z, err);
+        } else {
+            int32_t x0 = 0, x1 = 0;
+            if (!row_extent(X, r, x0, x1)) { err |= kRefillIndex; x1 = x0 = 0; }
+            for (int64_t cx = x0; cx < x1; cx += 64) {
+                const int nx = (int)min((int64_t)64, x1 - cx);
+                int32_t xk = 0;
+                double xv = 0.0;
+                if (lane < nx) { xk = X.ci[cx + lane]; xv = X.va[cx + lane]; }
+                for (int i = 0; i < nx; ++i) {
+                    WaveRow t{0, 0.0, false, 0};
+                    wave_feed_product<true>(t, lane, Y, Z, lane_get(xk, i), err);
+                    const double xt = lane_get(xv, i) * (alpha_inner * t.val);
+                    bool got = false;
+                    for (int s = 0; s < t.m; ++s) {
+                        const int32_t j = lane_get(t.col, s);
+                        const double v = lane_get(xt, s);
+                        if (lane < w.m && w.col == j) {
+                            w.val = w.hit ? w.val + v : v;
+                            w.hit = got = true;
+                        }
+                    }
+                    if (__popcll((unsigned long long)__builtin_amdgcn_ballot_w64(got)) != t.m) err |= kRefillMissing;
+                }
+            }
+        }
+        if (!err && lane < w.m) cva[c0 + lane] = w.hit ? alpha_outer * w.val : 0.0;
+    }
+    if (err && lane == 0) {
+        atomicOr(&errs[0], err);
+        atomicAdd(&errs[1], 1);
+    }
+}
+
 // ============================================================ helpers ====
 __global__ void k_csr_diag(Csr A, int32_t nrows, int32_t col_offset, double* diag, int* missing) {
     const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -5439,6 +5638,65 @@ int mpbp_spgemm_fill(const mpbp_csr* A, const mpbp_csr* B, double alpha, const i
                                                                      row_ptr, col_idx, val);
     MPBP_HIP(hipGetLastError());
     return MPBP_OK;
+}
+
+namespace {
+inline RCsr to_rcsr(const mpbp_csr* A) { return RCsr{A->row_ptr, A->col_idx, A->val, A->nrows, A->ncols, A->nnz}; }
+
+// launches k_refill<MODE> over C's rows, waits and turns the kernel's flags into a return code
+int run_refill(const char* who, int mode, const mpbp_csr* X, const mpbp_csr* Y, const mpbp_csr* Z, double alpha_inner,
+               double alpha_outer, const mpbp_csr* C, void* stream) {
+    if (C->nrows == 0) return MPBP_OK;
+    hipStream_t st = as_stream(stream);
+    int* d_err = nullptr;
+    MPBP_HIP(hipMalloc(&d_err, 2 * sizeof(int)));
+    hipError_t e = hipMemsetAsync(d_err, 0, 2 * sizeof(int), st);
+    if (e == hipSuccess) {
+        const unsigned grid = (unsigned)(((int64_t)C->nrows + kBlock / 64 - 1) / (kBlock / 64));
+        double* cval = const_cast<double*>(C->val);   // the one array a refill writes
+        const RCsr x = to_rcsr(X), y = to_rcsr(Y), z = Z ? to_rcsr(Z) : RCsr{nullptr, nullptr, nullptr, 0, 0, 0};
+        if (mode == kRefillPair) k_refill<kRefillPair><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
+        else if (mode == kRefillLeft) k_refill<kRefillLeft><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
+        else k_refill<kRefillRight><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
+        e = hipGetLastError();
+    }
+    int h[2] = {0, 0};
+    if (e == hipSuccess) e = hipMemcpyAsync(h, d_err, sizeof(h), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(d_err);
+    if (e != hipSuccess) return set_error(MPBP_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (h[0] & kRefillIndex) return set_error(MPBP_ERR_ARG, "%s: %d rows hold a row extent or column index out of range", who, h[1]);
+    if (h[0] & kRefillLong)
+        return set_error(MPBP_ERR_OVERFLOW, "%s: %d rows have an output or inner row wider than %d", who, h[1], kSpgemmMaxW);
+    if (h[0] & kRefillMissing)
+        return set_error(MPBP_ERR_PATTERN, "%s: %d rows of C lack a column their product holds", who, h[1]);
+    return MPBP_OK;
+}
+}  // namespace
+
+int mpbp_spgemm_refill(const mpbp_csr* A, const mpbp_csr* B, double alpha, const mpbp_csr* C, void* stream) {
+    int rc = check_csr(A);
+    if (!rc) rc = check_csr(B);
+    if (!rc) rc = check_csr(C);
+    if (rc) return rc;
+    if (A->ncols != B->nrows || C->nrows != A->nrows || C->ncols != B->ncols)
+        return set_error(MPBP_ERR_ARG, "spgemm_refill: shape mismatch");
+    return run_refill("spgemm_refill", kRefillPair, A, B, nullptr, 1.0, alpha, C, stream);
+}
+
+int mpbp_triple_refill(const mpbp_csr* X, const mpbp_csr* Y, const mpbp_csr* Z, int32_t assoc, double alpha_inner,
+                       double alpha_outer, const mpbp_csr* C, void* stream) {
+    int rc = check_csr(X);
+    if (!rc) rc = check_csr(Y);
+    if (!rc) rc = check_csr(Z);
+    if (!rc) rc = check_csr(C);
+    if (rc) return rc;
+    if (assoc != MPBP_ASSOC_LEFT && assoc != MPBP_ASSOC_RIGHT)
+        return set_error(MPBP_ERR_ARG, "triple_refill: assoc must be MPBP_ASSOC_LEFT or MPBP_ASSOC_RIGHT");
+    if (X->ncols != Y->nrows || Y->ncols != Z->nrows || C->nrows != X->nrows || C->ncols != Z->ncols)
+        return set_error(MPBP_ERR_ARG, "triple_refill: shape mismatch");
+    return run_refill("triple_refill", assoc == MPBP_ASSOC_LEFT ? kRefillLeft : kRefillRight, X, Y, Z, alpha_inner,
+                      alpha_outer, C, stream);
 }
 
 int64_t mpbp_plan_row_blocks(const int32_t* row_ptr, int32_t row_begin, int32_t row_end,

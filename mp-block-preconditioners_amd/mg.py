@@ -29,7 +29,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream_handle
-from .csr import DeviceCSR, DeviceSELL, csr_from_row_nnz, spgemm
+from .csr import DeviceCSR, DeviceSELL, csr_from_row_nnz, spgemm, timed_phase
 
 CELL, NODE = _lib.MG_CELL, _lib.MG_NODE
 # (row axis, column axis) kinds of [u_n, v_n, u_s, v_s]: u at (-(r+1/2) dy, c dx), v at (-r dy, (c+1/2) dx)
@@ -89,9 +89,10 @@ class StencilValues:
     slot order (so the interior sums are the CSR row's, bit for bit).  Rows within `reach` of the periodic edge are
     listed for the kernel's CSR path.  None when the operator is not of that form."""
 
-    def __init__(self, A: DeviceCSR, nf: int, m: int, reach: int, K: int, delta, vals, edge_rows):
+    def __init__(self, A: DeviceCSR, nf: int, m: int, reach: int, K: int, delta, vals, edge_rows, gather=None):
         self.A, self.nf, self.m, self.reach, self.slots = A, nf, m, reach, K
         self.delta, self.vals, self.edge_rows = delta, vals, edge_rows
+        self.gather = gather   # int32: vals[i] = A.val[gather[i]], the slot permutation build() found (refill)
         self._cs = _lib.Svl(nf, m, reach, K, delta.data_ptr(), vals.data_ptr(),
                             edge_rows.data_ptr() if edge_rows.numel() else None, int(edge_rows.numel()), 0)
 
@@ -102,8 +103,15 @@ class StencilValues:
     def build(cls, A: DeviceCSR, nf: int, m: int) -> "StencilValues | None":
         if A.shape != (nf * m * m, nf * m * m) or A.nnz == 0:
             return None
-        arrays = stencil_values_arrays(A.row_ptr, A.col_idx, A.val, nf, m)
+        arrays = _stencil_values_arrays(A.row_ptr, A.col_idx, A.val, nf, m)
         return None if arrays is None else cls(A, nf, m, *arrays)
+
+    def refill(self):
+        """The operator's current values scattered into the existing slot-major array by the permutation found at build
+        time (the pattern is the build's: nothing is verified again, nothing allocated)."""
+        if self.gather is None:
+            raise ValueError("this StencilValues was not made by build(): it has no slot permutation to refill by")
+        torch.index_select(self.A.val, 0, self.gather, out=self.vals)
 
     def matvec(self, x: torch.Tensor, out: torch.Tensor | None = None, mode=_lib.SPMV_STORE,
                z: torch.Tensor | None = None) -> torch.Tensor:
@@ -117,6 +125,12 @@ class StencilValues:
 def stencil_values_arrays(row_ptr: torch.Tensor, col_idx: torch.Tensor, val: torch.Tensor, nf: int, m: int):
     """(reach, K, delta[nf * K], vals[K * N] slot-major, edge_rows) of StencilValues from CSR arrays (any torch device),
     or None when the operator is not translation-invariant in that sense (see StencilValues)."""
+    arrays = _stencil_values_arrays(row_ptr, col_idx, val, nf, m)
+    return None if arrays is None else arrays[:5]
+
+
+def _stencil_values_arrays(row_ptr: torch.Tensor, col_idx: torch.Tensor, val: torch.Tensor, nf: int, m: int):
+    """stencil_values_arrays' tuple and the int32 entry index `gather` with vals[i] = val[gather[i]]."""
     N = nf * m * m
     if row_ptr.numel() != N + 1 or m < 4:
         return None
@@ -161,10 +175,14 @@ def stencil_values_arrays(row_ptr: torch.Tensor, col_idx: torch.Tensor, val: tor
     R += R & 1   # the kernel's interior cells go in pairs from an even column: an odd reach widens the edge band
     interior = (r >= R) & (r < m - R) & (c >= R) & (c < m - R)
     vals = torch.empty(K * N, dtype=torch.float64, device=dev)
-    vals[slot * N + rows] = val
+    where = slot * N + rows
+    vals[where] = val
+    gather = torch.empty(K * N, dtype=torch.int32, device=dev)   # (every slot seen once: `where` is a permutation)
+    gather[where] = torch.arange(K * N, dtype=torch.int32, device=dev)
+    del where
     row_int = interior.view(N, K)[:, 0]
     edge = torch.nonzero(~row_int).reshape(-1).to(torch.int32)
-    return R, K, delta.reshape(-1).contiguous(), vals, edge
+    return R, K, delta.reshape(-1).contiguous(), vals, edge, gather
 
 
 def set_transfer_kinds(mg_struct, fields, n0: int):
@@ -186,14 +204,19 @@ MAX_COARSE_ROWS = 8192   # the coarsest level's dense pseudo-inverse: 8192^2 dou
 COARSE_RCOND = 1e-11
 
 
+def _dense_inverse_host(A: DeviceCSR) -> np.ndarray:
+    """The pseudo-inverse dense_inverse_csr stores, on the host (row-major)."""
+    Ad = A.to_scipy().toarray()
+    return np.ascontiguousarray(np.linalg.pinv(Ad, rcond=COARSE_RCOND))
+
+
 def dense_inverse_csr(A: DeviceCSR) -> tuple[DeviceCSR, np.ndarray]:
     """The pseudo-inverse of a small operator as a CSR with every entry stored (rows of ncols entries)."""
     if A.shape[0] > MAX_COARSE_ROWS:
         raise ValueError(f"coarsest level has {A.shape[0]} rows (> {MAX_COARSE_ROWS}): its dense pseudo-inverse would "
                          f"need {A.shape[0] ** 2 * 8 / 1e9:.1f} GB and an O(m^3) factorisation; coarsening stops at an odd "
                          "grid size, so use a grid n = m 2^k with a small m (or a larger `coarsest`)")
-    Ad = A.to_scipy().toarray()
-    inv = np.ascontiguousarray(np.linalg.pinv(Ad, rcond=COARSE_RCOND))
+    inv = _dense_inverse_host(A)
     m = inv.shape[0]
     dev = A.device
     rp = np.arange(0, m * m + 1, m, dtype=np.int32)
@@ -307,6 +330,45 @@ class Multigrid:
         self.kernel_opts = _lib.kernel_opts(kernel_opts)
         self._mg.opts = ctypes.pointer(self.kernel_opts)
         set_transfer_kinds(self._mg, self.fields, n)
+
+    def refresh(self, diag: torch.Tensor | None = None, timings: dict | None = None):
+        """New values on the same grid: level 0's operator (the caller's) already holds them.  Recomputes, in place at
+        every address the hierarchy's struct holds, each coarser operator (one fused R (A P) launch per level,
+        mpbp_triple_refill, no A P intermediate), every level's diagonal and smoothing interval, the SELL and
+        stencil-values copies and the coarsest pseudo-inverse -- what a fresh Multigrid over the same operator computes,
+        bit for bit, with no structural work.  diag: level 0's new diagonal (default: recomputed; the tensor given to
+        the constructor, refreshed by the caller, may be passed again).  timings: seconds per phase, each synchronised.
+        Graphs captured before carry the old smoothing intervals as kernel arguments: capture again."""
+        for l, A in enumerate(self.ops):
+            if l > 0:
+                with timed_phase(timings, "galerkin"):
+                    check(lib().mpbp_triple_refill(ctypes.byref(self.R[l - 1].cstruct()),
+                                                   ctypes.byref(self.ops[l - 1].cstruct()),
+                                                   ctypes.byref(self.P[l - 1].cstruct()), _lib.ASSOC_RIGHT, 1.0, 1.0,
+                                                   ctypes.byref(A.cstruct()), stream_handle()))
+            with timed_phase(timings, "diag_bounds"):
+                d = self.diags[l]
+                if l == 0 and diag is not None:
+                    if diag.data_ptr() != d.data_ptr():
+                        d.copy_(diag)
+                else:
+                    d.copy_(A.diagonal())
+                lmax = A.gershgorin(d)
+                self.bounds[l] = (lmax / self.ratio, lmax)
+                self._levels[l].lmin, self._levels[l].lmax = self.bounds[l]
+        with timed_phase(timings, "layouts"):
+            for S in self.sells[0]:   # the transfers' copies hold geometry only
+                if S is not None:
+                    S.refill()
+            for V in self.svls:
+                if V is not None:
+                    V.refill()
+        with timed_phase(timings, "host_pinv"):
+            inv = _dense_inverse_host(self.ops[-1])
+            self.coarse_inv_host = inv
+            self.coarse_inv.val.copy_(torch.from_numpy(inv.reshape(-1)))
+            if self.coarse_dense is not None:
+                self.coarse_dense.copy_(torch.from_numpy(np.ascontiguousarray(inv.T)))
 
     def set_matrix_free_transfers(self, on: bool):
         """Name (on) or hide (off) the field kinds in the hierarchy's struct: with them the whole-grid levels' transfers

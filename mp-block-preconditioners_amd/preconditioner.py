@@ -108,6 +108,9 @@ class MultiphaseBlockPreconditioner:
     def set_theta_tables(self, cell, uface, vface):
         """Use caller-provided thn tables (any volume-fraction field; host arrays or tensors of n*n values, or
         scalars for a constant thn such as BASELINE configs[0]'s / solve.py:60-68's 0.75)."""
+        self._theta = self._as_tables(cell, uface, vface)
+
+    def _as_tables(self, cell, uface, vface):
         N = self.n * self.n
         tabs = []
         for a in (cell, uface, vface):
@@ -118,7 +121,16 @@ class MultiphaseBlockPreconditioner:
             if a.numel() != N:
                 raise ValueError("theta tables must have n*n entries")
             tabs.append(a)
-        self._theta = tuple(tabs)
+        return tuple(tabs)
+
+    def update_theta_tables(self, cell, uface, vface):
+        """New thn values (set_theta_tables' inputs) copied INTO the existing table tensors: every stencil, plan and
+        captured graph that holds their addresses sees the new field.  Creates the tables when there are none yet."""
+        if self._theta is None:
+            self._theta = self._as_tables(cell, uface, vface)
+            return
+        for dst, src in zip(self._theta, self._as_tables(cell, uface, vface)):
+            dst.copy_(src.reshape(dst.shape))
 
     def _params(self, c=1.0, d_u=-1.0, d_p=1.0, d_div=-1.0):
         return _lib.StokesParams(self.n, self.xi, self.eta_n, self.eta_s, float(c), float(d_u), float(d_p),
@@ -194,6 +206,44 @@ class MultiphaseBlockPreconditioner:
             D.stencil = PGStencil(prm, tabs[0], _lib.PG_D)
             G.stencil = PGStencil(prm, tabs[0], _lib.PG_G)
         return A, None, F, D, G
+
+    def refill(self, A, F, D, G, c, d_u, d_p: float = 1.0, d_div: float = -1.0):
+        """New values of get_big_A_matrix's operators in place (a time step: new thn tables -- update_theta_tables --
+        and coefficients on the same grid): mpbp_stokes_fill into each operator's own arrays, the values a fresh
+        get_big_A_matrix(c, d_u, d_p, d_div) holds bit for bit; no allocation, every address kept.  xi, eta_n and eta_s
+        are this object's current attributes.  The StokesParams the operators' stencils share are updated in place
+        (a plan's by-value copy is rewritten by ApproxSchurPreconditioner.refresh).  An operator may be None."""
+        cell, uface, vface = self.theta_tables()
+        prm = self._params(c, d_u, d_p, d_div)
+        ops = ((A, _lib.OP_A), (F, _lib.OP_F), (D, _lib.OP_D), (G, _lib.OP_G))
+        for M, op in ops:   # refuse everything before anything is written
+            if M is None:
+                continue
+            shape = (check(lib().mpbp_stokes_rows(self.n, op)), check(lib().mpbp_stokes_cols(self.n, op)))
+            if not isinstance(M, DeviceCSR) or M.shape != shape:
+                raise ValueError(f"refill: operator of shape {getattr(M, 'shape', None)} is not this n = {self.n} grid's "
+                                 f"{shape}")
+            st = getattr(M, "stencil", None)
+            if st is not None and st.cell.data_ptr() != cell.data_ptr():
+                raise ValueError("refill: the operator's stencil reads other thn tables than this object's (tables "
+                                 "replaced by set_theta_tables since it was built; use update_theta_tables)")
+        for M, op in ops:
+            if M is None:
+                continue
+            check(lib().mpbp_stokes_fill(ctypes.byref(prm), op, ptr(cell), ptr(uface), ptr(vface), ptr(M.row_ptr),
+                                         ptr(M.col_idx), ptr(M.val), stream_handle()))
+            st = getattr(M, "stencil", None)
+            if st is not None:
+                ctypes.memmove(ctypes.byref(st.prm), ctypes.byref(prm), ctypes.sizeof(prm))
+
+    @staticmethod
+    def refresh_products(F: DeviceCSR, D: DeviceCSR, G: DeviceCSR, GtG: DeviceCSR, GtFG: DeviceCSR):
+        """commutator_products' values recomputed into the existing Gt_G and Gt_F_G (same patterns, same bits):
+        Gt_F_G in one fused launch (mpbp_triple_refill) that never stores (-D) F."""
+        check(lib().mpbp_spgemm_refill(ctypes.byref(D.cstruct()), ctypes.byref(G.cstruct()), -1.0,
+                                       ctypes.byref(GtG.cstruct()), stream_handle()))
+        check(lib().mpbp_triple_refill(ctypes.byref(D.cstruct()), ctypes.byref(F.cstruct()), ctypes.byref(G.cstruct()),
+                                       _lib.ASSOC_LEFT, -1.0, 1.0, ctypes.byref(GtFG.cstruct()), stream_handle()))
 
     @staticmethod
     def commutator_products(F: DeviceCSR, D: DeviceCSR, G: DeviceCSR):

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream_handle
-from .csr import DeviceCSR
+from .csr import DeviceCSR, timed_phase
 from .preconditioner import MultiphaseBlockPreconditioner, PGStencil
 
 
@@ -142,6 +142,8 @@ class PlanProfiling:
                 if not a <= 1e-14 * m:
                     raise ValueError(f"q13_sym: this Gt_F_G is not symmetric (max |Q - Q^T| {a:.3g}, max |Q| {m:.3g})")
             setattr(self.kernel_opts, k, int(v))
+            if k == "q13_sym":
+                self._q13_sym_wanted = int(v)   # (refresh decides again from the refreshed values)
 
     def enable_profiling(self, capacity: int):
         evs = (ctypes.c_void_p * (2 * capacity))()
@@ -256,6 +258,10 @@ class ApproxSchurPreconditioner(PlanProfiling, spla.LinearOperator):
         # overrides -- later mpbp_set_* calls and other preconditioners' choices do not affect it
         self.kernel_opts = _lib.kernel_opts(kernel_opts)
         self.F, self.D, self.G = (_device_csr(M, dev) for M in (F, D, G))
+        self.generation = 0                                  # refresh() count
+        self._own_products = GtG is None or GtFG is None     # formed here: refresh(products="auto") recomputes them
+        self._q13_sym_wanted = self.kernel_opts.q13_sym      # the choice before the values' say (refresh asks again)
+        self._inner_spec = (inner_F or InnerSolver(), inner_P or InnerSolver())   # unresolved: refresh resolves again
         if GtG is None or GtFG is None:
             GtG, GtFG = MultiphaseBlockPreconditioner.commutator_products(self.F, self.D, self.G)
         self.GtG, self.GtFG = _device_csr(GtG, dev), _device_csr(GtFG, dev)
@@ -373,6 +379,58 @@ class ApproxSchurPreconditioner(PlanProfiling, spla.LinearOperator):
         p.f_numerics = _lib.NUMERICS_FAST if self.numerics == "fast" else _lib.NUMERICS_EXACT
         p.opts = ctypes.pointer(self.kernel_opts)
         return p
+
+    # -- a time step: new values, same grid ---------------------------------------------------------------
+    def refresh(self, products: str = "auto", timings: dict | None = None):
+        """Follow new operator values in place.  F, D and G already hold them (MultiphaseBlockPreconditioner.refill on
+        the same arrays).  Recomputes everything the apply reads that depends on values -- the commutator products,
+        both diagonals, the inner solves' intervals (explicit lmin / lmax stay, Gershgorin ones are recomputed), both
+        multigrid hierarchies, the SELL copies, the diamond values -- at the addresses the plan already holds, rewrites
+        the plan's by-value fields and takes again the decisions the constructor takes from values (fast numerics:
+        q13_sym only while the refreshed Gt_F_G is symmetric).  No structural work, no allocation kept: the result is a
+        freshly constructed preconditioner's, bit for bit.
+
+        products  "auto": the products this object formed itself are recomputed (refresh_products); a caller's GtG /
+                  GtFG are taken as already refreshed.  "given": both are taken as already refreshed.
+        timings   seconds per phase, each synchronised (None: no timing, no extra synchronisation).
+
+        Graphs captured before a refresh hold the old Chebyshev intervals as kernel arguments: they are stale, capture
+        again (fgmres's cached graph is dropped here)."""
+        if products not in ("auto", "given"):
+            raise ValueError("products must be 'auto' or 'given'")
+        if products == "auto" and self._own_products:
+            with timed_phase(timings, "products"):
+                MultiphaseBlockPreconditioner.refresh_products(self.F, self.D, self.G, self.GtG, self.GtFG)
+        with timed_phase(timings, "diag_bounds"):
+            self.diag_F.copy_(self.F.diagonal())
+            self.diag_P.copy_(self.GtG.diagonal())
+            self.inner_F = self._inner_spec[0].resolve(self.F, self.diag_F)
+            self.inner_P = self._inner_spec[1].resolve(self.GtG, self.diag_P)
+        if self.mg_F is not None:
+            self.mg_F.refresh(diag=self.diag_F, timings=timings)
+        if self.mg_P is not None:
+            self.mg_P.refresh(diag=self.diag_P, timings=timings)
+        with timed_phase(timings, "layouts"):
+            for S in self._sell or ():
+                S.refill()
+        with timed_phase(timings, "q13"):
+            if self.q13 is not None:
+                n, vals = self.q13
+                if lib().mpbp_q13_build(ctypes.byref(self.GtFG.cstruct()), n, ptr(vals), stream_handle()):
+                    raise _lib.MpbpError(f"refresh: Gt_F_G left the diamond layout: {lib().mpbp_last_error().decode()}")
+                if self.numerics == "fast":
+                    a = (ctypes.c_double * 2)()
+                    check(lib().mpbp_q13_asymmetry(n, ptr(vals), a, stream_handle()))
+                    self.q13_asymmetry = (a[0], a[1])
+                    self.kernel_opts.q13_sym = self._q13_sym_wanted if a[0] <= 1e-14 * a[1] else 0
+        p = self._plan
+        p.inner_F, p.inner_P = self.inner_F.cstruct(), self.inner_P.cstruct()
+        if self.f_stencil is not None:
+            p.f_prm = self.f_stencil.prm
+        elif self.pg_stencil is not None:
+            p.f_prm = self.pg_stencil.prm
+        self._fgmres_graph = None
+        self.generation += 1
 
     def sell_of(self, key):
         """The SELL-64 copy of F / D / G / P (Gt_G) / Q (Gt_F_G), or None in the CSR layout."""

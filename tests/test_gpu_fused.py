@@ -3,8 +3,11 @@
 k_gtg_solve runs a whole Chebyshev Gt_G solve (solve.py:265 / 271) as one tiled launch: level 0 (x0 = c2 b / diag)
 and every sweep recomputed over a shrinking halo in LDS, each row and update with the per-sweep kernels' IEEE
 operations -- so the apply must not change by a bit whether it is on (default) or off, in both F numerics, on grids
-smaller than, equal to and not a multiple of the 64 x 8 tile.  The exact apply with it on is also pinned against the
-oracle by tests/test_gpu_configs.py."""
+smaller than, equal to and not a multiple of its tile.  The tests here run its default form (32 x 16 tiles, kernel option
+gtg_solve_tile = 1) with the reference's coefficients (c = d_p = 1, d_u = -1); tests/test_gpu_fused_params.py runs
+both tile forms (64 x 8 too), both workgroup sizes and both right-hand-side forms, and the fused F launches, with general
+coefficients on the reference's and on random thn tables.  The exact apply with it on is also pinned against the oracle
+by tests/test_gpu_configs.py."""
 import numpy as np
 import pytest
 

@@ -42,13 +42,21 @@ def _tables(n, kind):
 
 # (tables, c, d_u, eta_n): the two fields, and one step that also changes the coefficients
 STEPS = [("smooth", 1.0, -1.0, 100.0), ("random", 1.0, -1.0, 100.0), ("smooth", 4.0, -0.5, 1e4)]
+# (tables, c, d_u, eta_n, xi, eta_s, d_p): every coefficient the steps above leave at 1 -- xi and eta_s (the fast F rows'
+# -d_u xi and d_u eta_s idx2) and d_p (2.5 switches the Gt_G rows' d_p == 1 specialisation off)
+STEP_ALL = ("random", 0.7, -1.5, 100.0, 2.5, 0.6, 2.5)
+
+
+def _unpack(step):
+    """(tables, c, d_u, eta_n, xi, eta_s, d_p) of a step; xi = eta_s = d_p = 1 where it does not name them."""
+    return tuple(step) + (1.0, 1.0, 1.0)[len(step) - 4:]
 
 
 def _fresh(n, step):
-    kind, c, d_u, eta_n = step
-    bp = _mp().MultiphaseBlockPreconditioner(n, 1.0, eta_n, 1.0)
+    kind, c, d_u, eta_n, xi, eta_s, d_p = _unpack(step)
+    bp = _mp().MultiphaseBlockPreconditioner(n, xi, eta_n, eta_s)
     bp.set_theta_tables(*_tables(n, kind))
-    A, _, F, D, G = bp.get_big_A_matrix(c=c, d_u=d_u)
+    A, _, F, D, G = bp.get_big_A_matrix(c=c, d_u=d_u, d_p=d_p)
     return bp, (A, F, D, G)
 
 
@@ -60,10 +68,10 @@ def _start(n):
 
 
 def _step_to(bp, ops, step, n):
-    kind, c, d_u, eta_n = step
+    kind, c, d_u, eta_n, xi, eta_s, d_p = _unpack(step)
     bp.update_theta_tables(*_tables(n, kind))
-    bp.eta_n = eta_n
-    bp.refill(*ops, c=c, d_u=d_u)
+    bp.xi, bp.eta_n, bp.eta_s = xi, eta_n, eta_s
+    bp.refill(*ops, c=c, d_u=d_u, d_p=d_p)
 
 
 def _same_values(got, ref, what=""):
@@ -310,9 +318,29 @@ def _pc(ops, inner, **kw):
 PAIRS = [("chebyshev:4", "chebyshev:4"), ("mg:2", "mg:1"), ("jacobi:3", "chebyshev:4")]
 
 
-def _refresh_walk(n, inner, **kw):
+def _same_with(pc, v, alt):
+    """The refreshed preconditioner's apply is the same bits with the kernel options `alt` (the launches a fused kernel
+    replaces: both read the refreshed state alike); the options are put back."""
+    if not alt:
+        return
+    got = pc.apply(v).clone()
+    before = {k: getattr(pc.kernel_opts, k) for k in alt}
+    pc.set_kernel_opts(**alt)
+    other = pc.apply(v).clone()
+    pc.set_kernel_opts(**before)
+    assert torch.equal(other, got), (alt, float((other - got).abs().max()))
+
+
+def _back_to_start(bp, ops, theta0):
+    bp.update_theta_tables(*theta0)
+    bp.xi, bp.eta_n, bp.eta_s = 1.0, 100.0, 1.0
+    bp.refill(*ops, c=1.0, d_u=-1.0)
+
+
+def _refresh_walk(n, inner, alt=None, **kw):
     """theta_0 -> smooth field -> random tables with new coefficients -> theta_0, the apply against a fresh
-    preconditioner's after each refresh, the original apply after the last; then a graph captured after the refreshes."""
+    preconditioner's after each refresh, the original apply after the last; then a graph captured after the refreshes.
+    alt: kernel options under which the refreshed apply must not change by a bit, checked after every refresh."""
     bp, ops = _start(n)
     theta0 = [t.clone() for t in bp.theta_tables()]
     pc = _pc(ops, inner, **kw)
@@ -330,13 +358,13 @@ def _refresh_walk(n, inner, **kw):
             (ref.inner_F.lmin, ref.inner_F.lmax, ref.inner_P.lmin, ref.inner_P.lmax)
         assert torch.equal(pc.apply(v), ref.apply(v)), step
         del ref, fops
-    bp.update_theta_tables(*theta0)
-    bp.eta_n = 100.0
-    bp.refill(*ops, c=1.0, d_u=-1.0)
+        _same_with(pc, v, alt)
+    _back_to_start(bp, ops, theta0)
     pc.refresh()
     assert pc.generation == 3 and id(pc._plan) == plan
     eager = pc.apply(v).clone()
     assert torch.equal(eager, first)
+    _same_with(pc, v, alt)   # (puts the options back: the capture below is the default launches')
     out = torch.empty_like(v)
     g = pc.capture(v, out)
     out.zero_()
@@ -354,6 +382,65 @@ def test_preconditioner_refresh_matches_fresh(n, numerics, inner):
 
 def test_preconditioner_refresh_csr_layout():
     _refresh_walk(16, PAIRS[1], layout="csr")
+
+
+# n = 96: every fused launch of the apply is taken (csrc/mpbp.hip: k_fsolve from n = 72, k_ftile 76, k_gtg_solve 78 for
+# four sweeps, k_fpre / k_gal1 / k_gal1p 72, k_gtg_level0 78, the level-1 <PRO> ascents 80) -- the kernels that read the
+# plan's by-value f_prm, the Chebyshev intervals and the multigrid levels a refresh rewrites
+N_FUSED = 96
+WALK_PAIRS = PAIRS + [("mg:1", "mg:1")]
+WALK_IDS = ["cheb-cheb", "mg2-mg1", "jacobi-cheb", "mg1-mg1"]
+
+
+def _per_sweep_opts(inner, numerics, n):
+    """The launches the fused kernels replace, for _same_with."""
+    if inner[0].startswith("mg"):
+        if numerics == "fast":
+            # below gal_fused_ok's n >= 72 the default level 1 is the stored Galerkin matrix, and the three matrix-free
+            # launches of mg_galerkin_mf = 1 are another summation order of it (test_matrix_free_galerkin_level1)
+            return dict(mg_fuse_l0=0, mg_galerkin_mf=1) if n >= 72 else dict(mg_fuse_l0=0)
+        return dict(f_solve=0, f_tile=0, gtg_fused=0, mg_fuse_l0=0)   # (exact: k_gtg_level0 is the fused launch there)
+    return dict(f_solve=0, f_tile=0, gtg_fused=0)
+
+
+@pytest.mark.parametrize("inner", WALK_PAIRS, ids=WALK_IDS)
+@pytest.mark.parametrize("numerics", ["exact", "fast"])
+def test_preconditioner_refresh_matches_fresh_fused_sizes(numerics, inner):
+    _refresh_walk(N_FUSED, inner, alt=_per_sweep_opts(inner, numerics, N_FUSED), numerics=numerics)
+
+
+@pytest.mark.parametrize("inner", PAIRS[:2], ids=WALK_IDS[:2])
+@pytest.mark.parametrize("numerics", ["exact", "fast"])
+@pytest.mark.parametrize("n", [32, N_FUSED])
+def test_refresh_follows_xi_eta_s_and_d_p(n, numerics, inner):
+    """STEP_ALL: xi, eta_s and d_p change too (bp.xi, bp.eta_s, refill's d_p) -- the operators, the intervals and the
+    apply are a freshly built preconditioner's, bit for bit, with the fused launches and with the per-sweep ones; and
+    the way back to theta_0 restores the first apply."""
+    bp, ops = _start(n)
+    theta0 = [t.clone() for t in bp.theta_tables()]
+    pc = _pc(ops, inner, numerics=numerics)
+    v = torch.from_numpy(np.random.default_rng(n + 4).standard_normal(pc.shape[0])).cuda()
+    first = pc.apply(v).clone()
+    _step_to(bp, ops, STEP_ALL, n)
+    pc.refresh()
+    _, fops = _fresh(n, STEP_ALL)
+    for name, M, ref in zip("AFDG", ops, fops):
+        _same_values(M, ref, name)
+    ref = _pc(fops, inner, numerics=numerics)
+    _same_values(pc.GtG, ref.GtG, "Gt_G")
+    _same_values(pc.GtFG, ref.GtFG, "Gt_F_G")
+    assert (pc.inner_F.lmin, pc.inner_F.lmax, pc.inner_P.lmin, pc.inner_P.lmax) == \
+        (ref.inner_F.lmin, ref.inner_F.lmax, ref.inner_P.lmin, ref.inner_P.lmax)
+    got = pc.apply(v).clone()
+    assert torch.equal(got, ref.apply(v))
+    assert not torch.equal(got, first)
+    alt = _per_sweep_opts(inner, numerics, n)
+    _same_with(pc, v, alt)
+    del ref, fops
+    _back_to_start(bp, ops, theta0)
+    pc.refresh()
+    assert torch.equal(pc.apply(v), first)
+    _same_with(pc, v, alt)
 
 
 def test_explicit_chebyshev_bounds_stay_fixed():

@@ -232,7 +232,17 @@ typedef struct mpbp_mg {
     int32_t tr_ky[8];
     int32_t tr_kx[8];
     const struct mpbp_kernel_opts* opts; /* optional: kernel choices of a standalone mpbp_mg_solve (NULL: defaults) */
+    /* Chebyshev acceleration of the `cycles` V-cycles (0: the stationary iteration; zero-initialised structs behave as
+     * before).  MPBP_MG_ACCEL_CHEBYSHEV: the fixed semi-iteration of mpbp_mg_accel_coeffs(accel_rho, cycles) over the
+     * same cycles -- spec(M A) in [1 - accel_rho, 1] for a symmetric cycle (pre == post) on a nonsingular symmetric A;
+     * still a linear operator, no inner products.  accel_x: two device vectors of level 0's length holding x_k and
+     * x_{k-1} across a cycle (the cycle's own buffers do not keep its initial guess).  One GPU only (part_levels 0). */
+    int32_t accel;
+    double accel_rho;                /* 0 < accel_rho < 1 */
+    double* accel_x[2];
 } mpbp_mg;
+#define MPBP_MG_ACCEL_NONE 0
+#define MPBP_MG_ACCEL_CHEBYSHEV 1
 
 /* The apply's operands.  On one GPU every matrix's columns index the full vector and the
  * *_bnd row blocks are empty.  Under a row partition the columns index the "ext" layout of the
@@ -568,6 +578,20 @@ int mpbp_mg_transfer_rows_fill(int32_t n, int32_t nfields, const int32_t* kinds,
 /* x_out = mg->cycles V-cycles for levels[0].A x = b from x = 0 (sub - x when sub != NULL).  Graph-capturable.
  * Row-partitioned hierarchies (part_levels > 0): b, sub, x_out hold the rank's owned rows of level 0. */
 int mpbp_mg_solve(const mpbp_mg* mg, const double* b, const double* sub, double* x_out, void* stream);
+/* Coefficients of the Chebyshev semi-iteration over K V-cycles with spec(M A) in [1 - rho, 1] (host, double;
+ * omega[K], mu[K]): theta = 1 - rho / 2, delta = rho / 2; omega[0] = 1 / theta, mu[0] = 0, r_0 = delta / theta;
+ * r_k = 1 / (2 theta / delta - r_{k-1}), omega[k] = 2 r_k / delta, mu[k] = r_k r_{k-1}.  Step k:
+ * x_{k+1} = x_k + omega[k] (V(b; x_k) - x_k) + mu[k] (x_k - x_{k-1}), x_0 = 0.  1 <= K <= 64 and 0 < rho < 1, else
+ * MPBP_ERR_ARG. */
+int mpbp_mg_accel_coeffs(double rho, int32_t K, double* omega, double* mu);
+/* One step's combination over n elements, every operation rounded separately in this order:
+ *   t1 = y - xk; t2 = omega t1; t3 = xk + t2; t4 = xk - xold; t5 = mu t4; x = t3 + t5;   out = x, or sub - x.
+ * xk == NULL and xold == NULL (step 0, x_0 = x_{-1} = 0): x = omega y.  xold == NULL alone (step 1, x_0 = 0): t4 = xk,
+ * the bits of xk - 0.  out may alias xold (or y, xk, sub): every
+ * element is read before it is written; partial overlaps are not supported.  16-byte accesses when every pointer is
+ * 16-byte aligned, else element-wise.  Graph-capturable. */
+int mpbp_mg_combine(int64_t n, const double* y, const double* xk, const double* xold, double omega, double mu,
+                    const double* sub, double* out, void* stream);
 
 /* ---- ghost rows over RCCL point-to-point (multi-GPU row partition) ------------------------------ */
 /* One RCCL group of neighbour sends / receives: the owned boundary rows (packed into one buffer per

@@ -20,6 +20,7 @@ INNER_JACOBI, INNER_CHEBYSHEV, INNER_MG = 0, 1, 2
 ASSOC_LEFT, ASSOC_RIGHT = 0, 1        # mpbp_triple_refill: (X Y) Z or X (Y Z)
 MG_CELL, MG_NODE = 0, 1
 MG_P, MG_R = 0, 1
+MG_ACCEL_NONE, MG_ACCEL_CHEBYSHEV = 0, 1   # mpbp_mg.accel
 HALO_BEGIN, HALO_END = 0, 1
 VEC_VELOCITY, VEC_PRESSURE = 0, 1
 PG_D, PG_G, PG_GTG = 0, 1, 2
@@ -142,7 +143,8 @@ class Mg(Structure):
                 ("coarse_inv_blocks", RowBlocks), ("coarse_dense", c_void_p),
                 ("part_levels", c_int32), ("gather_kind", c_int32), ("halo", HALO_FN), ("halo_ctx", c_void_p),
                 ("gather", GATHER_FN), ("tr_nfields", c_int32), ("tr_n0", c_int32), ("tr_ky", c_int32 * 8),
-                ("tr_kx", c_int32 * 8), ("opts", POINTER(KernelOpts))]
+                ("tr_kx", c_int32 * 8), ("opts", POINTER(KernelOpts)),
+                ("accel", c_int32), ("accel_rho", c_double), ("accel_x", c_void_p * 2)]
 
 
 class SchurPlan(Structure):
@@ -261,6 +263,8 @@ _SIGNATURES = {
     "mpbp_mg_transfer_rows_count": ([c_int32, c_int32, _P, c_int32, _P, c_int32, _P, _P], c_int),
     "mpbp_mg_transfer_rows_fill": ([c_int32, c_int32, _P, c_int32, _P, c_int32, _P, _P, _P, _P], c_int),
     "mpbp_mg_solve": ([POINTER(Mg), _P, _P, _P, _P], c_int),
+    "mpbp_mg_accel_coeffs": ([c_double, c_int32, _P, _P], c_int),
+    "mpbp_mg_combine": ([c_int64, _P, _P, _P, c_double, c_double, _P, _P, _P], c_int),
     "mpbp_gather": ([c_int32, _P, _P, _P, _P], c_int),
     "mpbp_scatter": ([c_int32, _P, _P, _P, _P], c_int),
     "mpbp_event_create": ([POINTER(c_void_p)], c_int),

@@ -7752,13 +7752,17 @@ bool f_pair_ok(const mpbp_schur_plan* p) { return p->f_numerics == MPBP_NUMERICS
 template <class Xch>
 int mg_smooth(const OpPair& op, int32_t nrows, const double* diag, double lmin, double lmax, int K, bool zero,
               const double* b, double** cur, double* alt, double* d, double* dst, const double* sub, hipStream_t st,
-              Xch&& xch, int s0 = 0) {
+              Xch&& xch, int s0 = 0, double* spare = nullptr) {
     double c1[64] = {}, c2[64] = {};
     if (K < 1 || K > 64) return set_error(MPBP_ERR_ARG, "mg: smoothing sweeps must be in [1, 64]");
     cheb_coeffs(lmin, lmax, K, c1, c2);
     const OpRef& o = op.in;
     double* x = *cur;
     double* other = alt;
+    // spare (a restart only): the iterate given in *cur is kept -- where the ping-pong would write back into it, the
+    // sweep writes `spare` instead
+    double* const keep = spare ? *cur : nullptr;
+    auto recycle = [&](double* v) { return v == keep ? spare : v; };
     int s = s0;   // s0 > 0: sweeps 0 .. s0 - 1 already ran from *cur's predecessor (d holds their direction)
     if (s0 && (zero || s0 >= K)) return set_error(MPBP_ERR_ARG, "mg: a smoothing resumed at sweep %d of %d", s0, K);
     if (zero && K >= 2 && op.bd.empty && o.stencil && !o.stencil->halo && o.which == 0 &&
@@ -7830,7 +7834,7 @@ int mg_smooth(const OpPair& op, int32_t nrows, const double* diag, double lmin, 
             a.dzero = dzero ? 1 : 0;
             rc = launch_ftile<false>(P, a, st);
             if (rc) return rc;
-            other = x;
+            other = recycle(x);
             x = out;
             break;
         }
@@ -7840,7 +7844,7 @@ int mg_smooth(const OpPair& op, int32_t nrows, const double* diag, double lmin, 
         const int rc = pair_cheb(op, x, b, diag, c1[s], c2[s], d, last ? sub : nullptr, nxt, st, last ? 0 : 1, dzero);
         dzero = false;
         if (rc) return rc;
-        other = x;
+        other = recycle(x);
         x = nxt;
     }
     *cur = x;
@@ -7982,7 +7986,10 @@ int mg_vcycle(const mpbp_mg* m, int l, const MgFine& fine, const double* b, bool
         if (rc) return rc;
         alt = cur == bx ? bt : bx;
     } else {
-        rc = mg_smooth(o, L.nrows, diag, L.lmin, L.lmax, L.pre, zero, b, &cur, alt, d, nullptr, nullptr, st, xch);
+        // an initial guess outside the level's two iterate buffers (the accelerated solve's x_k) is only read: the
+        // pre-smoothing then ping-pongs between bx and bt, and everything after it works on those two
+        double* spare = (!zero && xin != bx && xin != bt) ? bt : nullptr;
+        rc = mg_smooth(o, L.nrows, diag, L.lmin, L.lmax, L.pre, zero, b, &cur, alt, d, nullptr, nullptr, st, xch, 0, spare);
         if (rc) return rc;
         alt = cur == bx ? bt : bx;
         if (small) {   // r = b - A x and b_c = R r in one launch (k_grp_rr)
@@ -8069,12 +8076,128 @@ int mg_vcycle(const mpbp_mg* m, int l, const MgFine& fine, const double* b, bool
     return MPBP_OK;
 }
 
+// ---------------------------------------------------- Chebyshev acceleration of the V-cycles ----
+// Coefficients of the semi-iteration over K cycles with spec(M A) in [1 - rho, 1] (mpbp_mg_accel_coeffs; host, double).
+void mg_accel_coeffs(double rho, int K, double* omega, double* mu) {
+    const double theta = 1.0 - rho / 2.0;
+    const double delta = rho / 2.0;
+    double r = delta / theta;
+    omega[0] = 1.0 / theta;
+    mu[0] = 0.0;
+    for (int k = 1; k < K; ++k) {
+        const double r_new = 1.0 / (2.0 * theta / delta - r);
+        omega[k] = 2.0 * r_new / delta;
+        mu[k] = r_new * r;
+        r = r_new;
+    }
+}
+
+// One step's combination, x = xk + omega (y - xk) + mu (xk - xold), out = x or sub - x, in mpbp_mg_combine's operation
+// order (T: double or f64x2; the file is built without FMA contraction, so every operation rounds on its own).
+// xk NULL: x = omega y (x_0 = x_{-1} = 0); xold NULL: x_{k-1} = 0 is not read (xk - 0 is xk, bit for bit).  The forms
+// are told apart by the pointers, uniform over the grid: one kernel per access width instead of one per form.
+template <class T>
+__device__ inline T mg_combine_value(const T* y, const T* xk, const T* xold, const T* sub, double omega, double mu,
+                                     int64_t i) {
+    const T yv = y[i];
+    T x;
+    if (!xk) {
+        x = omega * yv;
+    } else {
+        const T xv = xk[i];
+        const T t1 = yv - xv;
+        const T t2 = omega * t1;
+        const T t3 = xv + t2;
+        const T t4 = xold ? xv - xold[i] : xv;
+        const T t5 = mu * t4;
+        x = t3 + t5;
+    }
+    return sub ? sub[i] - x : x;
+}
+// A pure stream: up to four 8-byte reads and one write per element.  VEC: 16 bytes per lane (every pointer 16-byte
+// aligned) and the odd last element by one lane; else one element per lane.  Grid-stride; the pointers carry no
+// __restrict__: out may be xold (or any other operand), each lane reads its elements before it writes them.
+template <bool VEC>
+__global__ void __launch_bounds__(kBlock) k_mg_combine(int64_t n, const double* y, const double* xk, const double* xold,
+                                                       double omega, double mu, const double* sub, double* out) {
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    const int64_t t0 = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (VEC) {
+        const int64_t n2 = n >> 1;
+        const f64x2 *y2 = reinterpret_cast<const f64x2*>(y), *xk2 = reinterpret_cast<const f64x2*>(xk),
+                    *xo2 = reinterpret_cast<const f64x2*>(xold), *sub2 = reinterpret_cast<const f64x2*>(sub);
+        f64x2* out2 = reinterpret_cast<f64x2*>(out);
+        for (int64_t i = t0; i < n2; i += stride) out2[i] = mg_combine_value(y2, xk2, xo2, sub2, omega, mu, i);
+        if ((n & 1) && t0 == 0) out[n - 1] = mg_combine_value(y, xk, xold, sub, omega, mu, n - 1);
+    } else {
+        for (int64_t i = t0; i < n; i += stride) out[i] = mg_combine_value(y, xk, xold, sub, omega, mu, i);
+    }
+}
+
+constexpr int kCombineMaxBlocks = 2048;   // 8 workgroups per CU; longer vectors stride
+
+int mg_combine(int64_t n, const double* y, const double* xk, const double* xold, double omega, double mu,
+               const double* sub, double* out, hipStream_t st) {
+    if (n < 0 || (n && (!y || !out)) || (!xk && xold))
+        return set_error(MPBP_ERR_ARG, "mg_combine: needs y and out, and xk whenever xold is given");
+    if (!n) return MPBP_OK;
+    const uintptr_t bits = (uintptr_t)y | (uintptr_t)xk | (uintptr_t)xold | (uintptr_t)sub | (uintptr_t)out;
+    const bool vec = (bits & 15) == 0;
+    const int64_t units = vec ? (n + 1) / 2 : n;
+    const unsigned grid = (unsigned)std::min<int64_t>((units + kBlock - 1) / kBlock, kCombineMaxBlocks);
+    if (vec) k_mg_combine<true><<<grid, kBlock, 0, st>>>(n, y, xk, xold, omega, mu, sub, out);
+    else k_mg_combine<false><<<grid, kBlock, 0, st>>>(n, y, xk, xold, omega, mu, sub, out);
+    MPBP_HIP(hipGetLastError());
+    return MPBP_OK;
+}
+
+// The accelerated form of mg_solve's loop: step k runs one V-cycle from x_k (step 0: the zero-start cycle, with its
+// fused level-0 launches) and combines its result y_k with x_k and x_{k-1}.  x_k and x_{k-1} live in m->accel_x: the
+// cycle ping-pongs between fine.x and fine.t and only reads an initial guess that is a third buffer (mg_smooth's
+// `spare`), so both survive it; the combination overwrites x_{k-1} with x_{k+1} (the last one writes
+// x_out, as sub - x when sub is set).
+int mg_solve_accel(const mpbp_mg* m, const MgFine& fine, const double* b, double* x_out, const double* sub,
+                   hipStream_t st) {
+    const int K = m->cycles;
+    if (m->accel != MPBP_MG_ACCEL_CHEBYSHEV) return set_error(MPBP_ERR_ARG, "mg: unknown acceleration %d", m->accel);
+    if (m->part_levels > 0)
+        return set_error(MPBP_ERR_ARG, "mg: Chebyshev acceleration is not available on a row-partitioned hierarchy "
+                                       "(part_levels = %d): use accel = 0 there", m->part_levels);
+    if (K > 64 || !(m->accel_rho > 0.0) || !(m->accel_rho < 1.0))
+        return set_error(MPBP_ERR_ARG, "mg: acceleration needs cycles <= 64 and 0 < accel_rho < 1 (got %d, %g)", K,
+                         m->accel_rho);
+    double* X[2] = {m->accel_x[0], m->accel_x[1]};
+    if (K > 1 && (!X[0] || !X[1] || X[0] == X[1]))
+        return set_error(MPBP_ERR_ARG, "mg: acceleration needs two distinct accel_x vectors");
+    for (int i = 0; i < 2 && K > 1; ++i)
+        if (X[i] == fine.x || X[i] == fine.t || X[i] == fine.r || X[i] == fine.d || X[i] == x_out || X[i] == b ||
+            X[i] == sub)
+            return set_error(MPBP_ERR_ARG, "mg: accel_x must not alias the level-0 work buffers, b, sub or x_out");
+    double omega[64], mu[64];
+    mg_accel_coeffs(m->accel_rho, K, omega, mu);
+    const int64_t n = m->levels[0].nrows;
+    int xk = 0;   // X[xk] = x_k, X[1 - xk] = x_{k-1} (k >= 1)
+    for (int k = 0; k < K; ++k) {
+        const bool last = k == K - 1;
+        double* y = nullptr;
+        int rc = mg_vcycle(m, 0, fine, b, k == 0, k == 0 ? fine.x : X[xk], nullptr, nullptr, &y, st);
+        if (rc) return rc;
+        double* out = last ? x_out : X[k == 0 ? 0 : 1 - xk];
+        rc = mg_combine(n, y, k >= 1 ? X[xk] : nullptr, k >= 2 ? X[1 - xk] : nullptr, omega[k], mu[k],
+                        last ? sub : nullptr, out, st);
+        if (rc) return rc;
+        if (k > 0) xk = 1 - xk;
+    }
+    return MPBP_OK;
+}
+
 // x_out = mg^-1 b by mg->cycles V-cycles from x = 0 (sub - that when sub != NULL).
 int mg_solve(const mpbp_mg* m, const MgFine& fine, const double* b, double* x_out, const double* sub, hipStream_t st) {
     if (!m || m->nlevels < 2 || !m->levels || m->cycles < 1 || !m->coarse_inv.row_ptr)
         return set_error(MPBP_ERR_ARG, "mg: hierarchy needs >= 2 levels, >= 1 cycle and the coarse inverse");
     if (x_out == fine.x || x_out == fine.t || x_out == fine.r || x_out == fine.d || b == x_out)
         return set_error(MPBP_ERR_ARG, "mg: x_out must not alias the level-0 work buffers or b");
+    if (m->accel) return mg_solve_accel(m, fine, b, x_out, sub, st);
     double* cur = fine.x;
     for (int k = 0; k < m->cycles; ++k) {
         const bool last = k == m->cycles - 1;
@@ -8804,6 +8927,18 @@ int mpbp_mg_transfer_rows_fill(int32_t n, int32_t nfields, const int32_t* kinds,
                                                                      rows);
     MPBP_HIP(hipGetLastError());
     return MPBP_OK;
+}
+
+int mpbp_mg_accel_coeffs(double rho, int32_t K, double* omega, double* mu) {
+    if (K < 1 || K > 64 || !omega || !mu || !(rho > 0.0) || !(rho < 1.0))
+        return set_error(MPBP_ERR_ARG, "mg_accel_coeffs: need 1 <= K <= 64 and 0 < rho < 1");
+    mg_accel_coeffs(rho, K, omega, mu);
+    return MPBP_OK;
+}
+
+int mpbp_mg_combine(int64_t n, const double* y, const double* xk, const double* xold, double omega, double mu,
+                    const double* sub, double* out, void* stream) {
+    return mg_combine(n, y, xk, xold, omega, mu, sub, out, as_stream(stream));
 }
 
 int mpbp_mg_solve(const mpbp_mg* mg, const double* b, const double* sub, double* x_out, void* stream) {

@@ -1032,6 +1032,10 @@ class DistributedSchurPreconditioner(PlanProfiling):
                  device=None, layout="sell", f_mode="auto", pg_mode="auto", halo="auto", self_halo=False,
                  halo_overlap=False, ca="auto", fuse_g=True, mg_min_cells=1 << 14, mg_part_levels=None,
                  local_products=True, numerics="exact", kernel_opts=None):
+        for name, inner in (("inner_F", inner_F), ("inner_P", inner_P)):   # (before any torch.distributed call)
+            if getattr(inner, "accel", None) is not None:
+                raise ValueError(f"{name}: Chebyshev-accelerated multigrid (accel={inner.accel!r}) is not available on "
+                                 "the row-partitioned hierarchies; use accel=None here")
         import torch.distributed as dist
         from .preconditioner import MultiphaseBlockPreconditioner
         from .solve import InnerSolver, _check_numerics

@@ -202,6 +202,13 @@ MAX_COARSE_ROWS = 8192   # the coarsest level's dense pseudo-inverse: 8192^2 dou
 # solve's output carried a ~1e17 constant.  The next singular values are 9e-2 (Gt_G) and, for F, 7.5e-6 (eta ratio
 # 100) / 7.5e-8 (10^4) (tools/coarse_spectrum.py): 1e-11 sits orders of magnitude from both.
 COARSE_RCOND = 1e-11
+# Chebyshev acceleration (accel="chebyshev"): the interval's rho = ACCEL_RHO_MARGIN x the largest of the power iteration's
+# last three ratios (Multigrid.contraction).  The ratios still climb after 8 steps (0.037 -> 0.090 for F at 64^2), so the
+# estimate sits below the spectral radius; the margin covers part of that and the iteration tolerates the rest (an
+# eigenvalue just outside the interval is still damped), while rho = 0.15 there already loses the gain.
+ACCEL_RHO_MARGIN = 1.1
+ACCEL_RHO_MAX = 0.5      # an estimate at or above this: a singular operator (E keeps its null space) or no contraction
+ACCELS = (None, "chebyshev")
 
 
 def _dense_inverse_host(A: DeviceCSR) -> np.ndarray:
@@ -249,12 +256,26 @@ class Multigrid:
              grouped small-level kernel is not (kernel option mg_group_rows)
     kernel_opts  overrides of the process-default kernel choices for this hierarchy's standalone solve (_lib.KernelOpts
              field names)
+    accel    None: ``cycles`` stationary V-cycles x <- x + M (b - A x).  "chebyshev": the fixed Chebyshev semi-iteration
+             over the same ``cycles`` V-cycles for spec(M A) in [1 - rho, 1] (mpbp_mg_accel_coeffs, mpbp_mg_combine) --
+             no inner products, no extra operator apply, still a linear operator.  Needs a symmetric cycle (pre ==
+             post) and a nonsingular operator.
+    rho      the contraction bound of one V-cycle; None: estimated here (and again by refresh) as ACCEL_RHO_MARGIN x
+             the largest of contraction()'s last three ratios -- setup work that synchronises with the host
     """
 
     def __init__(self, A: DeviceCSR, n: int, fields=FIELDS_PRESSURE, pre: int = 2, post: int = 2, cycles: int = 1,
                  ratio: float = 4.0, coarsest: int = 8, diag: torch.Tensor | None = None, sell: bool = True,
-                 fine_sell: bool = True, svl_min_rows: int | None | str = "default", kernel_opts: dict | None = None):
+                 fine_sell: bool = True, svl_min_rows: int | None | str = "default", kernel_opts: dict | None = None,
+                 accel: str | None = None, rho: float | None = None):
         nf = len(fields)
+        if accel not in ACCELS:
+            raise ValueError(f"accel must be one of {ACCELS}, not {accel!r}")
+        if accel is not None and pre != post:
+            raise ValueError(f"accel={accel!r} needs a symmetric cycle, pre == post (got V({pre},{post})): the "
+                             "Chebyshev interval [1 - rho, 1] holds for a symmetric M only")
+        if rho is not None and (accel is None or not 0.0 < float(rho) < 1.0):
+            raise ValueError("rho needs accel and 0 < rho < 1")
         if A.shape != (nf * n * n, nf * n * n):
             raise ValueError(f"operator {A.shape} is not {nf} fields of a {n} x {n} grid")
         if n < 4 or n % 2 or n // 2 < 2:
@@ -330,6 +351,57 @@ class Multigrid:
         self.kernel_opts = _lib.kernel_opts(kernel_opts)
         self._mg.opts = ctypes.pointer(self.kernel_opts)
         set_transfer_kinds(self._mg, self.fields, n)
+        # Chebyshev acceleration: x_k and x_{k-1} (the cycle's own buffers do not keep its initial guess), and rho
+        self.accel = accel
+        self.rho_estimated = accel is not None and rho is None
+        self._rho = None if rho is None else float(rho)
+        self.accel_x = None
+        if accel is not None:
+            self.accel_x = [torch.zeros(self.ops[0].shape[0], **f64) for _ in range(2)]
+            for i, t in enumerate(self.accel_x):
+                self._mg.accel_x[i] = t.data_ptr()
+            if self.rho_estimated:
+                self._rho = self.estimate_rho()
+            self._mg.accel_rho = self._rho
+            self._mg.accel = _lib.MG_ACCEL_CHEBYSHEV
+
+    @property
+    def rho(self) -> float | None:
+        """The accelerated iteration's contraction bound (None without accel)."""
+        return self._rho
+
+    def contraction(self, steps: int = 8, seed: int = 0) -> list[float]:
+        """Power iteration on the error propagator E = I - M A of ONE zero-start V-cycle M over the stored level-0
+        operator: e_0 = numpy.random.default_rng(seed).standard_normal (host), e_{j+1} = e_j - V(A e_j); returns
+        ||e_{j+1}||_2 / ||e_j||_2 per step.  The ratios climb towards E's spectral radius.  Setup work: allocates and
+        synchronises with the host."""
+        A = self.ops[0]
+        e = torch.from_numpy(np.random.default_rng(seed).standard_normal(A.shape[0])).to(self.device)
+        saved = (self._mg.cycles, self._mg.accel)
+        self._mg.cycles, self._mg.accel = 1, _lib.MG_ACCEL_NONE
+        try:
+            ratios = []
+            norm = float(torch.linalg.vector_norm(e))
+            Ae, Ve = torch.empty_like(e), torch.empty_like(e)
+            for _ in range(steps):
+                A.matvec(e, out=Ae)
+                self.solve(Ae, out=Ve)
+                e = e - Ve
+                new = float(torch.linalg.vector_norm(e))
+                ratios.append(new / norm)
+                norm = new
+        finally:
+            self._mg.cycles, self._mg.accel = saved
+        return ratios
+
+    def estimate_rho(self) -> float:
+        """ACCEL_RHO_MARGIN x the largest of contraction()'s last three ratios; ValueError at ACCEL_RHO_MAX or above."""
+        rho = ACCEL_RHO_MARGIN * max(self.contraction()[-3:])
+        if not rho < ACCEL_RHO_MAX:
+            raise ValueError(f"accel={self.accel!r}: the estimated contraction bound rho = {rho:.3g} is not below "
+                             f"{ACCEL_RHO_MAX}: the operator is singular (its null space gives I - M A an eigenvalue of "
+                             "1) or the cycle does not contract; use the stationary cycles (accel=None)")
+        return rho
 
     def refresh(self, diag: torch.Tensor | None = None, timings: dict | None = None):
         """New values on the same grid: level 0's operator (the caller's) already holds them.  Recomputes, in place at
@@ -338,7 +410,9 @@ class Multigrid:
         stencil-values copies and the coarsest pseudo-inverse -- what a fresh Multigrid over the same operator computes,
         bit for bit, with no structural work.  diag: level 0's new diagonal (default: recomputed; the tensor given to
         the constructor, refreshed by the caller, may be passed again).  timings: seconds per phase, each synchronised.
-        Graphs captured before carry the old smoothing intervals as kernel arguments: capture again."""
+        An estimated acceleration rho is estimated again (phase "accel_rho"; an explicit one stays).
+        Graphs captured before carry the old smoothing intervals (and the acceleration's coefficients) as kernel
+        arguments: capture again."""
         for l, A in enumerate(self.ops):
             if l > 0:
                 with timed_phase(timings, "galerkin"):
@@ -369,6 +443,10 @@ class Multigrid:
             self.coarse_inv.val.copy_(torch.from_numpy(inv.reshape(-1)))
             if self.coarse_dense is not None:
                 self.coarse_dense.copy_(torch.from_numpy(np.ascontiguousarray(inv.T)))
+        if self.rho_estimated:   # (an explicit rho stays)
+            with timed_phase(timings, "accel_rho"):
+                self._rho = self.estimate_rho()
+                self._mg.accel_rho = self._rho
 
     def set_matrix_free_transfers(self, on: bool):
         """Name (on) or hide (off) the field kinds in the hierarchy's struct: with them the whole-grid levels' transfers
@@ -383,7 +461,7 @@ class Multigrid:
         return self._mg
 
     def solve(self, b: torch.Tensor, out: torch.Tensor | None = None, sub: torch.Tensor | None = None) -> torch.Tensor:
-        """x = MG^-1 b (``cycles`` V-cycles from 0); sub - x when sub is given."""
+        """x = MG^-1 b (``cycles`` V-cycles from 0, accelerated when accel is set); sub - x when sub is given."""
         n0 = self.ops[0].shape[0]
         assert b.is_cuda and b.dtype == torch.float64 and b.numel() == n0
         if out is None:
@@ -393,4 +471,5 @@ class Multigrid:
 
     def __repr__(self):
         return (f"Multigrid(levels={self.sizes}, fields={len(self.fields)}, pre={self.pre}, post={self.post}, "
-                f"cycles={self.cycles}, ratio={self.ratio})")
+                f"cycles={self.cycles}, ratio={self.ratio}"
+                + (f", accel={self.accel!r}, rho={self._rho:.4g}" if self.accel else "") + ")")

@@ -38,6 +38,9 @@ class InnerSolver:
     lmin   lower end of the Chebyshev interval; None -> lmax / ratio
     pre, post, smooth_ratio, coarsest   "mg" only: smoothing sweeps per level, smoothing interval
            [lmax / smooth_ratio, lmax], coarsening stops at n <= coarsest
+    accel, rho   "mg" only: accel="chebyshev" runs the `sweeps` V-cycles as a fixed Chebyshev semi-iteration (about 40x
+           per cycle instead of 12x for F; needs pre == post and a nonsingular operator, so F, not Gt_G); rho is one
+           cycle's contraction bound, None -> estimated at construction and on every refresh (mg.Multigrid)
     """
     kind: str = "chebyshev"
     sweeps: int = 4
@@ -48,13 +51,32 @@ class InnerSolver:
     post: int = 2
     smooth_ratio: float = 4.0
     coarsest: int = 16     # dense coarsest inverse at 16^2: 1024 x 1024 for F (one fewer latency-bound level than 8^2)
+    accel: str | None = None
+    rho: float | None = None
+
+    def __post_init__(self):
+        self._check_accel()
+
+    def _check_accel(self):
+        if self.accel is None and self.rho is None:
+            return
+        if self.kind != "mg":
+            raise ValueError(f"accel / rho accelerate multigrid V-cycles: kind must be 'mg', not {self.kind!r}")
+        if self.accel != "chebyshev":
+            raise ValueError(f"accel must be None or 'chebyshev', not {self.accel!r}")
+        if int(self.pre) != int(self.post):
+            raise ValueError(f"accel='chebyshev' needs a symmetric cycle, pre == post (got V({self.pre},{self.post}))")
+        if self.rho is not None and not 0.0 < float(self.rho) < 1.0:
+            raise ValueError(f"rho must lie in (0, 1), not {self.rho!r}")
 
     def resolve(self, M: DeviceCSR, diag: torch.Tensor) -> "InnerSolver":
+        self._check_accel()
         if self.kind == "jacobi":
             return InnerSolver("jacobi", int(self.sweeps), 0.0, 0.0, self.ratio)
         if self.kind == "mg":
             return InnerSolver("mg", int(self.sweeps), 0.0, 0.0, self.ratio, int(self.pre), int(self.post),
-                               float(self.smooth_ratio), int(self.coarsest))
+                               float(self.smooth_ratio), int(self.coarsest), self.accel,
+                               None if self.rho is None else float(self.rho))
         if self.kind != "chebyshev":
             raise ValueError(f"unknown inner solver {self.kind!r}")
         lmax = float(self.lmax) if self.lmax is not None else M.gershgorin(diag)
@@ -64,7 +86,8 @@ class InnerSolver:
     def multigrid(self, M: DeviceCSR, n: int, fields, diag: torch.Tensor):
         from .mg import Multigrid
         return Multigrid(M, n, fields, pre=self.pre, post=self.post, cycles=int(self.sweeps),
-                         ratio=self.smooth_ratio, coarsest=self.coarsest, diag=diag, fine_sell=False)
+                         ratio=self.smooth_ratio, coarsest=self.coarsest, diag=diag, fine_sell=False,
+                         accel=self.accel, rho=self.rho)
 
     def cstruct(self):
         kind = {"chebyshev": _lib.INNER_CHEBYSHEV, "jacobi": _lib.INNER_JACOBI, "mg": _lib.INNER_MG}[self.kind]

@@ -2098,12 +2098,15 @@ struct FStencilFast : FStencilDev {
     struct Co { double w, c, nn, kc, ks, ke, xu, xv; };
     __device__ Co coeffs(const Nb& t) const {
         const double wc = t.w + t.c;
+        return coeffs_k(t.w, t.c, t.nn, wc, 0.25 * ((t.nw + t.nn) + wc), 0.25 * (wc + (t.sw + t.s)),
+                        0.25 * ((t.nn + t.ne) + (t.c + t.e)));
+    }
+    // the same from the node averages (k_fsolve_w reads them from its LDS table); wc = w + c
+    __device__ Co coeffs_k(double w, double c, double nn, double wc, double kc, double ks, double ke) const {
         Co k;
-        k.w = t.w; k.c = t.c; k.nn = t.nn;
-        k.kc = 0.25 * ((t.nw + t.nn) + wc);
-        k.ks = 0.25 * (wc + (t.sw + t.s));
-        k.ke = 0.25 * ((t.nn + t.ne) + (t.c + t.e));
-        const double hu = 0.5 * wc, hv = 0.5 * (t.nn + t.c);
+        k.w = w; k.c = c; k.nn = nn;
+        k.kc = kc; k.ks = ks; k.ke = ke;
+        const double hu = 0.5 * wc, hv = 0.5 * (nn + c);
         const double mx = -d_u * xi;             // -d_u xi h (1 - h): the same for both phases (h_s = 1 - h_n)
         k.xu = mx * (hu * (1.0 - hu));
         k.xv = mx * (hv * (1.0 - hv));
@@ -3524,7 +3527,9 @@ int launch_fsolve_t(const FStencilFast& P, const FSolve& a, hipStream_t st, cons
 // the rows is computed once: the node averages K(r, c) into an LDS table (FStencilFast::coeffs' kc / ks / ke are
 // K(r, c), K(r + 1, c), K(r, c + 1), the same sums in the same order), and each owned cell keeps its XI couplings and
 // identity weights in registers (in place of its two face values), so a level reads 6 coefficients instead of 8
-// thn values and skips ~27 of the row's ~115 fp64 operations.  (An in-place variant -- one x image, a second barrier
+// thn values and skips ~27 of the row's ~115 fp64 operations.  Level 0 reads the table too (one more barrier, no node
+// average computed twice); thn, x_p and the table are staged by wave-uniform rows, and an owned cell's global and LDS
+// indices all derive from one wrapped (row, column) pair and one tile-relative (dr, dc) pair.  (An in-place variant -- one x image, a second barrier
 // per level, 34 KB of LDS for three workgroups per CU -- spilled ~700 B per lane at the 168-VGPR cap and ran 4.5x
 // slower: removed.)
 template <int TW, int TH, int H>
@@ -3552,6 +3557,31 @@ __device__ inline void fs_ring_cell_t(int r, int j, int r0, int c0, int& vr, int
         vc = (k & 1) ? c0 + TW - 1 + r : c0 - r;
     }
 }
+// the same cell of ring r (a constant where it is called) as offsets from the corner of the tile + h
+template <int TW, int TH>
+__device__ inline void fs_ring_rel(int r, int j, int h, int& dr, int& dc) {
+    const int w = TW + 2 * r, k = j - 2 * w;
+    const bool top = j < w, row = j < 2 * w;
+    dr = h + (row ? (top ? -r : TH - 1 + r) : 1 - r + (k >> 1));
+    dc = h + (row ? (top ? j : j - w) - r : ((k & 1) ? TW - 1 + r : -r));
+}
+// base[off / 8] with base wave-uniform and off a 32-bit byte offset: the scalar-base form of the global access
+template <class V>
+__device__ inline V* at_off(V* base, uint32_t off) { return (V*)((const char*)base + off); }
+__device__ inline double ld_off(const double* base, uint32_t off) { return *at_off(base, off); }
+template <int W>
+struct TRelT {   // staged thn around one cell: t points at it, W columns per staged row
+    const double* t;
+    __device__ double T(int sph, int r, int c) const {
+        const double v = t[r * W + c];
+        return sph ? 1.0 - v : v;
+    }
+};
+template <int W, int N>
+struct XRelT {   // 4 fields ([4][N], W columns per row) around one cell: x points at its field-0 entry
+    const double* x;
+    __device__ double X(int f, int r, int c) const { return x[f * N + r * W + c]; }
+};
 template <int TW, int TH, int H, bool SUB, bool PART, class BS>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) MPBP_LDS_READS
 k_fsolve_w(FStencilFast P, FSolve a, BS bs) {
@@ -3562,8 +3592,10 @@ k_fsolve_w(FStencilFast P, FSolve a, BS bs) {
     constexpr int NT = T::NT;
     constexpr int NSL = NT + 2;   // owned cells per lane: NT tile cells, slot A (rings 1 .. H - 1), slot B (ring H)
     constexpr int NS = NT + 1;    // ... with updates after x0 (ring H only needs x0)
-    constexpr int PW = T::RW + 1, PN = PW * (T::RH + 1);   // BS: x_p over the tile + H, + its west / north neighbours
-    constexpr int KW = T::RW + 1, KN = KW * (T::RH + 1);   // node averages K(r, c) of the tile + H, + 1 row / column
+    constexpr int PW = T::RW + 1, PH = T::RH + 1, PN = PW * PH;   // BS: x_p over the tile + H, + its west / north neighbours
+    // node averages K(r, c) of the tile + H, + 1 row / column: ks / ke of every level-0 cell, ring H included
+    constexpr int KW = T::RW + 1, KN = KW * (T::RH + 1);
+    static_assert(T::TSW <= 64 && PW == KW, "a staged row is one wave's lanes; x_p's window and the K table share indices");
     __shared__ double ts[T::TSN];
     __shared__ double kt[KN];
     __shared__ double xa[4 * T::N], xb[4 * T::N];
@@ -3583,118 +3615,136 @@ k_fsolve_w(FStencilFast P, FSolve a, BS bs) {
             return P.wrap(vr);
         }
     };
-    {
-        constexpr int IT = (T::TSN + 255) / 256;
+    // Staging by rows: wave w takes staged rows w, w + 4, ..., lane l column l.  A row's wrapped global base is
+    // scalar work, the wrapped column is the lane's own for every row (x_p's window starts at the same (rbt, cbt)), and
+    // an iteration is one load or one LDS store at an immediate offset from the lane's base.
+    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6) & 3;
+    const uint32_t gcs = 8u * (uint32_t)P.wrap(cbt + (lane < T::TSW ? lane : 0));   // (byte offsets: n n 8 < 2^32)
+    if (lane < T::TSW) {
+        constexpr int IT = (T::TSH + 3) / 4;
         double v[IT];
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 256;
-            if (i < T::TSN) {
-                const int sr = i / T::TSW, sc = i - sr * T::TSW;
-                v[it] = P.cell[P.wrap(rbt + sr) * n + P.wrap(cbt + sc)];
-            }
+            const int sr = wv + 4 * it;
+            if (sr < T::TSH) v[it] = ld_off(P.cell + P.wrap(rbt + sr) * n, gcs);
         }
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 256;
-            if (i < T::TSN) ts[i] = v[it];
+            const int sr = wv + 4 * it;
+            if (sr < T::TSH) ts[sr * T::TSW + lane] = v[it];
         }
     }
     if constexpr (BS::on) {
-        constexpr int IT = (PN + 255) / 256;
-        double v[IT];
+        if (lane < PW) {
+            constexpr int IT = (PH + 3) / 4;
+            double v[IT];
 #pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 256;
-            if (i < PN) {
-                const int sr = i / PW, sc = i - sr * PW;
-                const int pr = in_row(rb - 1 + sr, PART ? bs.h : 0);
-                v[it] = bs.xp[(PART ? ext_row(1, 0, pr, P.L, bs.h, n) : pr * n) + P.wrap(cb - 1 + sc)];
+            for (int it = 0; it < IT; ++it) {
+                const int sr = wv + 4 * it;
+                if (sr < PH) {
+                    const int pr = in_row(rbt + sr, PART ? bs.h : 0);
+                    v[it] = ld_off(bs.xp + (PART ? ext_row(1, 0, pr, P.L, bs.h, n) : pr * n), gcs);
+                }
+            }
+#pragma unroll
+            for (int it = 0; it < IT; ++it) {
+                const int sr = wv + 4 * it;
+                if (sr < PH) ps[sr * PW + lane] = v[it];
             }
         }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 256;
-            if (i < PN) ps[i] = v[it];
-        }
     }
-    const int lane = tid & 63, wv = tid >> 6;
-    int cr[NSL], cc[NSL], rr[NSL];
-    bool own[NSL];
+    // owned cells at (dr, dc) from the corner (rb, cb) of the tile + H: one LDS index per cell, neighbours at
+    // immediate offsets (xi: the x levels, xi + dr: the K table and x_p, xi + 2 dr + TSW + 1: thn)
+    int dr[NSL], dc[NSL];
 #pragma unroll
     for (int m = 0; m < NT; ++m) {   // tile cell m: row (tid / TW) + m (256 / TW), column tid % TW
-        cr[m] = r0 + tid / TW + m * (256 / TW); cc[m] = c0 + tid % TW; own[m] = true; rr[m] = 0;
+        dr[m] = H + tid / TW + m * (256 / TW); dc[m] = H + tid % TW;
     }
-    {   // slot A: rings 1 .. H - 1 in consecutive lane ranges; slot B: ring H
-        int r = 0, j = 0, base = 0;
+    // slot A: rings 1 .. H - 1 in consecutive lane ranges (the ring is the range's: compile time); slot B: ring H
+    int rA = 0;   // slot A's ring, 0: none
+    dr[NT] = H; dc[NT] = H;
+    {
+        int base = 0;
 #pragma unroll
         for (int q = 1; q < H; ++q) {
-            if (r == 0 && lane < base + T::q(q)) {
-                r = q;
-                j = wv * T::q(q) + lane - base;
+            if (lane >= base && lane < base + T::q(q)) {
+                fs_ring_rel<TW, TH>(q, wv * T::q(q) + lane - base, H, dr[NT], dc[NT]);
+                rA = q;
             }
             base += T::q(q);
         }
-        own[NT] = r != 0;
-        rr[NT] = r;
-        fs_ring_cell_t<TW, TH>(r ? r : 1, j, r0, c0, cr[NT], cc[NT]);
-        own[NT + 1] = lane < T::q(H);
-        rr[NT + 1] = H;
-        fs_ring_cell_t<TW, TH>(H, own[NT + 1] ? wv * T::q(H) + lane : 0, r0, c0, cr[NT + 1], cc[NT + 1]);
     }
+    const bool ownB = lane < T::q(H);
+    fs_ring_rel<TW, TH>(H, ownB ? wv * T::q(H) + lane : 0, H, dr[NT + 1], dc[NT + 1]);
+    auto own = [&](int sl) { return sl < NT || (sl == NT ? rA != 0 : ownB); };
+    // one wrapped (gr, gc) and k = gr n + gc per cell: faces, b, sub and the output (a tile cell inside the grid is
+    // its own wrapped cell) index from it: a 32-bit byte offset from the field's base (n n 8 < 2^32)
     double fl[NSL][2], bl[BS::on ? 1 : NSL][4];
+    uint32_t kg[NSL];
+    bool ww[NSL], wn[NSL], outok[NT];
 #pragma unroll
     for (int sl = 0; sl < NSL; ++sl) {
-        if (!own[sl]) continue;
-        const int gr = P.wrap(cr[sl]), gc = P.wrap(cc[sl]);
-        const int32_t k = gr * n + gc;
-        fl[sl][0] = P.uface[k];
-        fl[sl][1] = P.vface[k];
+        if (!own(sl)) continue;
+        const int vr = rb + dr[sl], vc = cb + dc[sl];
+        // (a tile cell's column is never negative, nor its row on the whole grid)
+        const int gr = !PART && sl < NT ? (vr >= n ? vr - n : vr) : P.wrap(vr);
+        const int gc = sl < NT ? (vc >= n ? vc - n : vc) : P.wrap(vc);
+        kg[sl] = 8u * (uint32_t)(gr * n + gc);
+        ww[sl] = gc == 0;
+        wn[sl] = gr == 0;
+        if (sl < NT) outok[sl < NT ? sl : 0] = vr < hi && vc < n;   // else a tile past the last row / column
+        fl[sl][0] = ld_off(P.uface, kg[sl]);
+        fl[sl][1] = ld_off(P.vface, kg[sl]);
         if constexpr (!BS::on) {
-            const int br = in_row(cr[sl], P.h);
+            if constexpr (PART) {
+                const int br = in_row(vr, P.h);
 #pragma unroll
-            for (int f = 0; f < 4; ++f) bl[sl][f] = a.b[(PART ? ext_row(4, f, br, P.L, P.h, n) : (f * n + br) * n) + gc];
-        }
-    }
-    __syncthreads();
-    const TTileT<T::TSW> tt{ts, rbt, cbt};
-    // the node averages every level reads (FStencilFast::coeffs' kc of cell (r, c), ks of (r - 1, c), ke of (r, c - 1):
-    // the same sum in the same order), computed once; first read after level 1's barrier
-    {
-        constexpr int IK = (KN + 255) / 256;
+                for (int f = 0; f < 4; ++f) bl[sl][f] = a.b[ext_row(4, f, br, P.L, P.h, n) + gc];
+            } else {
 #pragma unroll
-        for (int it = 0; it < IK; ++it) {
-            const int i = tid + it * 256;
-            if (i < KN) {
-                const int r = rb + i / KW, c = cb + i % KW;
-                kt[i] = 0.25 * ((tt.T(0, r - 1, c - 1) + tt.T(0, r - 1, c)) + (tt.T(0, r, c - 1) + tt.T(0, r, c)));
+                for (int f = 0; f < 4; ++f) bl[sl][f] = ld_off(a.b + (size_t)f * nn, kg[sl]);
             }
         }
     }
+    __syncthreads();
+    // the node averages every level reads (FStencilFast::coeffs' kc of cell (r, c), ks of (r - 1, c), ke of (r, c - 1):
+    // the same sum in the same order), computed once, by rows as the staging; level 0 reads them too
+    if (lane < KW) {
+        constexpr int IK = (T::RH + 1 + 3) / 4;
+#pragma unroll
+        for (int it = 0; it < IK; ++it) {
+            const int kr = wv + 4 * it;
+            if (kr < T::RH + 1) {
+                const double* t = ts + kr * T::TSW + lane;   // thn(rb + kr - 1, cb + lane - 1)
+                kt[kr * KW + lane] = 0.25 * ((t[0] + t[1]) + (t[T::TSW] + t[T::TSW + 1]));
+            }
+        }
+    }
+    __syncthreads();
     // per owned cell: d, its reciprocal diagonals, b, and the level-invariant row terms (XI couplings xu / xv, weights)
     double d[NS][4], rd[NS][4], bv[NS][4], kx[NS][2];
     typename FStencilFast::W4 wt[NS];
     // level 0: x0 = d0 = c2_0 b / diag over the tile + H
 #pragma unroll
     for (int sl = 0; sl < NSL; ++sl) {
-        if (!own[sl]) continue;
-        const int vr = cr[sl], vc = cc[sl];
-        const int gr = P.wrap(vr), gc = P.wrap(vc);
+        if (!own(sl)) continue;
+        const int si = dr[sl] * T::RW + dc[sl], ki = si + dr[sl];
+        const double* t = ts + (ki + dr[sl] + T::TSW + 1);   // thn at the cell
         const FStencilDev::Cell cl{{fl[sl][0], fl[sl][1]}};
-        const typename FStencilFast::Co k = P.coeffs(P.nb(tt, vr, vc));
+        const double tw = t[-1], tc = t[0], tn = t[-T::TSW];
+        const typename FStencilFast::Co k = P.coeffs_k(tw, tc, tn, tw + tc, kt[ki], kt[ki + KW], kt[ki + 1]);
         const typename FStencilFast::W4 w = P.weights(cl);
         double b4[4], r4[4];
         P.rdiag4_co(k, w, r4);
         if constexpr (BS::on) {
-            const int pi = (vr - rb + 1) * PW + (vc - cb + 1);
+            const int pi = ki + PW + 1;
             const typename BS::Q q{ps[pi], ps[pi - 1], ps[pi - PW]};
 #pragma unroll
-            for (int f = 0; f < 4; ++f) b4[f] = bs.b_at(f, vr, vc, gc == 0, gr == 0, tt, q);
+            for (int f = 0; f < 4; ++f) b4[f] = bs.b_at(f, 0, 0, ww[sl], wn[sl], TRelT<T::TSW>{t}, q);
         } else {
 #pragma unroll
             for (int f = 0; f < 4; ++f) b4[f] = bl[sl][f];
         }
-        const int si = (vr - rb) * T::RW + (vc - cb);
 #pragma unroll
         for (int f = 0; f < 4; ++f) {
             const double x0 = a.c2_0 * b4[f] * r4[f];
@@ -3717,38 +3767,39 @@ k_fsolve_w(FStencilFast P, FSolve a, BS bs) {
 #pragma unroll
     for (int l = 1; l <= H; ++l) {
         __syncthreads();
-        const XTileT<T::RW, T::RH> xt{cur, rb, cb};
         const double c1 = a.c1[l - 1], c2 = a.c2[l - 1];
+        // tile cell m's entry of field f in the output's layout (the row partition keeps its layout's own addressing)
+        auto out_at = [&](auto* v, int m, int f) {
+            if constexpr (PART) return v + P.out_row(f, rb + dr[m] - P.r0, cb + dc[m]);
+            else return at_off(v + (size_t)f * nn, kg[m]);
+        };
         if constexpr (SUB) {
             if (l == H) {
 #pragma unroll
                 for (int m = 0; m < NT; ++m) {
-                    const int vr = cr[m], vc = cc[m];
-                    if (vr >= hi || vc >= n) continue;
+                    if (!outok[m]) continue;
 #pragma unroll
-                    for (int f = 0; f < 4; ++f)
-                        sv[m][f] = a.sub[PART ? P.out_row(f, vr - P.r0, vc) : f * nn + vr * n + vc];
+                    for (int f = 0; f < 4; ++f) sv[m][f] = *out_at(a.sub, m, f);
                 }
             }
         }
 #pragma unroll
         for (int sl = 0; sl < NS; ++sl) {
-            if (sl >= NT && (!own[sl] || rr[sl] > H - l)) continue;   // ring r lives through level H - r
-            const int vr = cr[sl], vc = cc[sl];
-            if (l == H && (vr >= hi || vc >= n)) continue;            // a tile past the last row / column
+            if (sl >= NT && (l == H || rA == 0 || rA > H - l)) continue;   // ring r lives through level H - r
+            if (l == H && !outok[sl < NT ? sl : 0]) continue;
+            const int si = dr[sl] * T::RW + dc[sl], ki = si + dr[sl];
+            const double* t = ts + (ki + dr[sl] + T::TSW + 1);
             typename FStencilFast::Co k;
-            k.w = tt.T(0, vr, vc - 1);
-            k.c = tt.T(0, vr, vc);
-            k.nn = tt.T(0, vr - 1, vc);
-            const int ki = (vr - rb) * KW + (vc - cb);
+            k.w = t[-1];
+            k.c = t[0];
+            k.nn = t[-T::TSW];
             k.kc = kt[ki];
             k.ks = kt[ki + KW];
             k.ke = kt[ki + 1];
             k.xu = kx[sl][0];
             k.xv = kx[sl][1];
             double acc[4];
-            P.rows4_co(vr, vc, k, wt[sl], xt, acc);
-            const int si = (vr - rb) * T::RW + (vc - cb);
+            P.rows4_co(0, 0, k, wt[sl], XRelT<T::RW, T::N>{cur + si}, acc);
 #pragma unroll
             for (int f = 0; f < 4; ++f) {
                 const double z = (bv[sl][f] - acc[f]) * rd[sl][f];
@@ -3758,9 +3809,8 @@ k_fsolve_w(FStencilFast P, FSolve a, BS bs) {
                     d[sl][f] = dn;
                 } else {
                     const double x = cur[f * T::N + si] + dn;
-                    const int32_t o = PART ? P.out_row(f, vr - P.r0, vc) : f * nn + vr * n + vc;
-                    if constexpr (SUB) a.x_out[o] = sv[sl < NT ? sl : 0][f] - x;
-                    else a.x_out[o] = x;
+                    if constexpr (SUB) *out_at(a.x_out, sl < NT ? sl : 0, f) = sv[sl < NT ? sl : 0][f] - x;
+                    else *out_at(a.x_out, sl < NT ? sl : 0, f) = x;
                 }
             }
         }

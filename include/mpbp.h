@@ -13,6 +13,7 @@
  *   mpbp_spgemm_*         Gt_G = np.matmul(mD, G), Gt_F_G = (mD F) G          solve.py:246-249
  *   mpbp_spmv             b_approx = np.matmul(A, u_vec)                      apply.py:72
  *                         A @ xk in the FGMRES residual callback              solve.py:166
+ *   mpbp_stokes_apply     the same products with A's rows recomputed from thn (nothing assembled)
  *   mpbp_jacobi_*         Jacobi(A, b, N, x)                                  solve.py:149-159
  *   mpbp_cheb_*           inner Chebyshev sweeps (BASELINE.json configs[3])
  *   mpbp_f_stencil_*      the F products / sweeps above with F's rows recomputed from thn
@@ -490,6 +491,16 @@ int mpbp_gtg_stencil_cheb_step(const mpbp_stokes_params* prm, const double* cell
  * hold a tile and its halos (n >= 72 + 2 (sweeps - 1)), else MPBP_ERR_ARG and nothing is launched. */
 int mpbp_gtg_stencil_cheb_solve(const mpbp_stokes_params* prm, const double* cell, const double* b, const double* diag,
                                 double lmin, double lmax, int32_t sweeps, double* x_out, void* stream);
+
+/* ---- matrix-free system matrix ------------------------------------------------------------------- */
+/* y = op(A x), A = [[F, d_p G], [d_div D, 0]] (preconditioner.py:339-341; np.matmul(A, u_vec), apply.py:72) recomputed
+ * per row from the thn tables: the assembled A's mpbp_spmv bit for bit; with MPBP_SPMV_FAST in mode the tolerance-mode
+ * F rows (pressure rows and G products unchanged).  x, y: 5 n^2 doubles, x != y; z for ADD / RESID.  One GPU, n >= 3.
+ * One launch (kernel option march_rows: grid rows per workgroup), no allocation or synchronisation.  MPBP_ERR_ARG for
+ * a null prm, table or vector, x == y, a missing z, n < 3 or an unknown mode; MPBP_ERR_OVERFLOW for 5 n^2 > INT32_MAX;
+ * nothing is launched then. */
+int mpbp_stokes_apply(const mpbp_stokes_params* prm, const double* cell, const double* uface, const double* vface,
+                      int32_t mode, const double* x, const double* z, double* y, void* stream);
 
 /* ---- kernel choices ------------------------------------------------------------------------------ */
 /* Which kernel form runs each step.  Every choice gives the same results as every other (bit-identical), except

@@ -14,6 +14,7 @@ OP_A, OP_F, OP_D, OP_G = 0, 1, 2, 3
 OP_L_N, OP_L_S, OP_D_N, OP_D_S, OP_G_N, OP_G_S, OP_XI_N, OP_XI_S = range(4, 12)
 SPMV_STORE, SPMV_ADD, SPMV_RESID = 0, 1, 2
 OK, ERR_ARG = 0, -1                    # mpbp.h return codes (MPBP_OK, MPBP_ERR_ARG)
+ERR_OVERFLOW = -3                     # MPBP_ERR_OVERFLOW
 SPMV_FAST = 0x100                     # mpbp_f_stencil_spmv: tolerance-mode F rows
 NUMERICS_EXACT, NUMERICS_FAST = 0, 1  # mpbp_schur_plan.f_numerics
 INNER_JACOBI, INNER_CHEBYSHEV, INNER_MG = 0, 1, 2
@@ -209,6 +210,7 @@ _SIGNATURES = {
     "mpbp_f_stencil_cheb_step": ([POINTER(StokesParams), _P, _P, _P, POINTER(RowPart), _P, _P, c_double, c_double,
                                   _P, _P, _P, _P], c_int),
     "mpbp_pg_stencil_spmv": ([POINTER(StokesParams), _P, POINTER(RowPart), c_int32, c_int32, _P, _P, _P, _P], c_int),
+    "mpbp_stokes_apply": ([POINTER(StokesParams), _P, _P, _P, c_int32, _P, _P, _P, _P], c_int),
     "mpbp_gtg_stencil_jacobi_step": ([POINTER(StokesParams), _P, POINTER(RowPart), _P, _P, _P, _P, _P], c_int),
     "mpbp_gtg_stencil_cheb_step": ([POINTER(StokesParams), _P, POINTER(RowPart), _P, _P, c_double, c_double, _P, _P,
                                     _P, _P], c_int),

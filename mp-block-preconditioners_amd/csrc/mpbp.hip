@@ -1050,6 +1050,25 @@ struct EpiResid {
     __device__ void apply(int32_t r, double acc, const P& p) const { st_stream<NT>(y + r, p.z - acc); }
     __device__ void operator()(int32_t r, double acc, const P& p) const { apply<false>(r, acc, p); }
 };
+// EpiAdd / EpiResid with z loaded once the row's sum is known instead of ahead of it (pre requests nothing): the
+// five-row A policy (StokesADev) has no registers left to hold five z values through its rows at k_march's 4 waves
+// per SIMD -- with EpiAdd / EpiResid its instances spilled 24-72 B per lane.  Same operation, same bits.
+struct EpiAddLate {
+    const double* z;
+    double* y;
+    struct P {};
+    __device__ P pre(int32_t) const { return {}; }
+    __device__ P pre_lite(int32_t) const { return {}; }
+    __device__ void operator()(int32_t r, double acc, const P&) const { y[r] = acc + ld_stream(z + r); }
+};
+struct EpiResidLate {
+    const double* z;
+    double* y;
+    struct P {};
+    __device__ P pre(int32_t) const { return {}; }
+    __device__ P pre_lite(int32_t) const { return {}; }
+    __device__ void operator()(int32_t r, double acc, const P&) const { y[r] = ld_stream(z + r) - acc; }
+};
 // The solver epilogues carry two run-time switches -- `sub` (the solve's last sweep returns sub - x) and
 // `store_d` (the direction is stored except on a solve's last sweep).  The marching kernels get them as
 // template flags instead (FIXED = true; launch_march picks the instance): no load or store then sits under
@@ -1183,6 +1202,8 @@ template <class E> struct RcpOk : std::false_type {};
 template <> struct RcpOk<EpiStore> : std::true_type {};
 template <> struct RcpOk<EpiAdd> : std::true_type {};
 template <> struct RcpOk<EpiResid> : std::true_type {};
+template <> struct RcpOk<EpiAddLate> : std::true_type {};
+template <> struct RcpOk<EpiResidLate> : std::true_type {};
 template <bool S> struct RcpOk<EpiJacobiT<true, S, true>> : std::true_type {};
 template <bool S, bool D, bool B> struct RcpOk<EpiChebT<true, S, D, B, true>> : std::true_type {};
 template <bool S, bool D, bool B> struct RcpOk<EpiChebFirstT<true, S, D, B, true>> : std::true_type {};
@@ -1212,6 +1233,14 @@ template <>
 __device__ inline void set_x<EpiAddX0::P>(EpiAddX0::P&, double) {}
 template <>
 __device__ inline void set_diag<EpiAddX0::P>(EpiAddX0::P&, double) {}
+template <>
+__device__ inline void set_x<EpiAddLate::P>(EpiAddLate::P&, double) {}
+template <>
+__device__ inline void set_diag<EpiAddLate::P>(EpiAddLate::P&, double) {}
+template <>
+__device__ inline void set_x<EpiResidLate::P>(EpiResidLate::P&, double) {}
+template <>
+__device__ inline void set_diag<EpiResidLate::P>(EpiResidLate::P&, double) {}
 
 // CSR SpMV over the same row blocks, one wavefront per 64-row quarter of a block and no block-wide
 // barrier.  Each wave streams its rows' [row_ptr[ra], row_ptr[rb]) entries in chunks of kWaveCap with
@@ -4051,6 +4080,108 @@ struct GStencilDev : PGDev {
     }
 };
 
+// y = A x, A = [[F, d_p G], [d_div D, 0]] (build_row's MPBP_OP_A; np.matmul(A, u_vec), apply.py:72): the five rows
+// of a cell -- u_n, v_n, u_s, v_s and pressure -- from the five staged fields [u_n | v_n | u_s | v_s | p], one
+// marching launch, nothing assembled.  FS is the F policy (FStencilDev, FStencilDevM<M>, FStencilFast) whose rows
+// the velocity rows start from.  Exact numerics reproduce the assembled row's sequential sum: a velocity row is F's
+// row sum with the two G products added to the SAME accumulator ((F-sum + g1) + g2: G's columns 4N + ... sort after
+// all of F's), in GStencilDev::row's order; the pressure row is DStencilDev::row's eight products in its order,
+// each entry d_div * (inv * avg) as the assembly forms it (phase_D_row's value scaled by d_div).  With FStencilFast
+// the velocity rows start from the regrouped rows (rows4); the G products and the pressure row are the exact ones
+// (explicit operations, the file is built without contraction), so pressure rows agree bit for bit in both modes.
+// One GPU, whole-grid layouts, n >= 3.
+template <class FS>
+struct StokesADev : FS {
+    double d_p, d_div, inv, minv;   // inv = 1.0 / dx, minv = -1.0 / dx as phase_D_row / phase_G_row evaluate them
+    static constexpr int NF = 5, NOUT = 5;
+    __device__ int32_t xrow(int f, int gr) const { return (f * this->n + this->wrap(gr)) * this->n; }
+    __device__ int32_t out_row(int o, int lr, int gc) const { return (o * this->n + lr) * this->n + gc; }
+    // velocity row o's two G products added to acc: the wrapped neighbour sorts last
+    template <bool EDGE, class TA, class XA>
+    __device__ double add_g(double acc, int o, int gr, int gc, const TA& ta, const XA& xa) const {
+        const int p = o >> 1;
+        const double t0 = ta.T(p, gr, gc), xC = xa.X(4, gr, gc);
+        if ((o & 1) == 0) {   // u row: entries p(gr, gc-1), p(gr, gc)
+            const double gu = 0.5 * (t0 + ta.T(p, gr, gc - 1));
+            const double uC = (d_p * (inv * gu)) * xC, uW = (d_p * (minv * gu)) * xa.X(4, gr, gc - 1);
+            const bool wrapw = EDGE && gc == 0;
+            acc += wrapw ? uC : uW;
+            acc += wrapw ? uW : uC;
+        } else {              // v row: entries p(gr-1, gc), p(gr, gc)
+            const double gv = 0.5 * (t0 + ta.T(p, gr - 1, gc));
+            const double vC = (d_p * (minv * gv)) * xC, vN = (d_p * (inv * gv)) * xa.X(4, gr - 1, gc);
+            const bool wrapn = EDGE && gr == 0;
+            acc += wrapn ? vC : vN;
+            acc += wrapn ? vN : vC;
+        }
+        return acc;
+    }
+    // pressure row: phase n then phase s, the wrapped neighbour first
+    template <bool EDGE, class TA, class XA>
+    __device__ double p_row(int gr, int gc, const TA& ta, const XA& xa) const {
+        const int n = this->n;
+        const bool lastc = EDGE && gc == n - 1, lastr = EDGE && gr == n - 1;
+        double acc = 0.0;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const double t0 = ta.T(p, gr, gc), tE = ta.T(p, gr, gc + 1), tW = ta.T(p, gr, gc - 1);
+            const double tN = ta.T(p, gr - 1, gc), tS = ta.T(p, gr + 1, gc);
+            const double uE = (d_div * (inv * (0.5 * (t0 + tE)))) * xa.X(2 * p, gr, gc + 1);
+            const double uC = (d_div * (minv * (0.5 * (t0 + tW)))) * xa.X(2 * p, gr, gc);
+            const double vC = (d_div * (inv * (0.5 * (t0 + tN)))) * xa.X(2 * p + 1, gr, gc);
+            const double vS = (d_div * (minv * (0.5 * (t0 + tS)))) * xa.X(2 * p + 1, gr + 1, gc);
+            acc += lastc ? uE : uC;
+            acc += lastc ? uC : uE;
+            acc += lastr ? vS : vC;
+            acc += lastr ? vC : vS;
+        }
+        return acc;
+    }
+    template <bool EDGE, class TA, class XA>
+    __device__ double row(int o, int gr, int gc, const TA& ta, const XA& xa, double* dg,
+                          const typename FS::Cell& cl) const {
+        if (o == 4) {
+            *dg = 0.0;
+            return p_row<EDGE>(gr, gc, ta, xa);
+        }
+        return add_g<EDGE>(FS::template row<EDGE>(o, gr, gc, ta, xa, dg, cl), o, gr, gc, ta, xa);
+    }
+    // tolerance mode (FS = FStencilFast): the five rows at once; no diagonal is handed over (rd unused by the
+    // store / add / residual epilogues)
+    template <class TA, class XA>
+    __device__ void rows4(int gr, int gc, const TA& ta, const XA& xa, const typename FS::Cell& cl, double* acc,
+                          double* rd) const {
+        FS::template rows4<false>(gr, gc, ta, xa, cl, acc, rd);
+#pragma unroll
+        for (int o = 0; o < 4; ++o) acc[o] = add_g<true>(acc[o], o, gr, gc, ta, xa);
+        acc[4] = p_row<true>(gr, gc, ta, xa);
+#pragma unroll
+        for (int o = 0; o < 5; ++o) rd[o] = 0.0;
+    }
+};
+
+template <class Epi>
+int launch_stokes_a(const FStencilDev& P, double d_p, double d_div, const double* x, Epi epi, hipStream_t st,
+                    bool fast) {
+    const double dx = 1.0 / P.n;
+    auto go = [&](const auto& Q) {
+        using S = StokesADev<std::decay_t<decltype(Q)>>;
+        const S A{Q, d_p, d_div, 1.0 / dx, -1.0 / dx};
+        const int64_t chunks = march_chunks(A, KO().march_rows, march_capacity<k_march<S, XPlain, Epi, BNone>>());
+        if (chunks == 0) return (int)MPBP_OK;
+        const int64_t strips = (A.n + kMB - 1) / kMB;
+        k_march<S, XPlain, Epi, BNone><<<(unsigned)(chunks * strips), kMB, 0, st>>>(A, XPlain{x}, (int)chunks, epi, BNone{});
+        MPBP_HIP(hipGetLastError());
+        return (int)MPBP_OK;
+    };
+    if constexpr (std::is_same_v<Epi, EpiStore>) return with_f_policy(P, fast, go);
+    // ADD / RESID: the M = 13 and M = 5 identity instances spilled (8 / 24 B per lane) beside the z operand; these
+    // modes take the general exact rows there (the same bits: the identities only skip exactly known multiplies)
+    if (fast) return go(FStencilFast{P});
+    if (P.d_u == -1.0 && P.eta_s == 1.0 && P.eta_n == 1.0) return go(FStencilDevM<7>{P});
+    return go(P);
+}
+
 // Gt_G = -(D G): row (gr, gc) has the five entries N, W, C, E, S (grid neighbours).  Each off-diagonal
 // gets one product per phase; the diagonal gets four per phase, accumulated in D's column order.
 struct GtGStencilDev : PGDev {
@@ -6765,6 +6896,31 @@ int mpbp_pg_stencil_spmv(const mpbp_stokes_params* prm, const double* cell, cons
     case MPBP_PG_G: return pg_spmv(GStencilDev{P}, mode, x, z, y, st);
     case MPBP_PG_GTG: return pg_spmv(GtGStencilDev{P}, mode, x, z, y, st);
     default: return set_error(MPBP_ERR_ARG, "pg_stencil_spmv: unknown operator %d", op);
+    }
+}
+
+int mpbp_stokes_apply(const mpbp_stokes_params* prm, const double* cell, const double* uface, const double* vface,
+                      int32_t mode, const double* x, const double* z, double* y, void* stream) {
+    // every refusal comes before the first HIP call
+    if (!prm || !cell || !uface || !vface)
+        return set_error(MPBP_ERR_ARG, "stokes_apply: needs the parameters and the three thn tables");
+    const bool fast = (mode & MPBP_SPMV_FAST) != 0;
+    mode &= ~MPBP_SPMV_FAST;
+    if (mode != MPBP_SPMV_STORE && mode != MPBP_SPMV_ADD && mode != MPBP_SPMV_RESID)
+        return set_error(MPBP_ERR_ARG, "stokes_apply: unknown mode %d", mode);
+    if (!x || !y || x == y || (mode != MPBP_SPMV_STORE && !z))
+        return set_error(MPBP_ERR_ARG, "stokes_apply: bad vectors (x, y distinct and non-null; z for ADD / RESID)");
+    if (prm->n < 3) return set_error(MPBP_ERR_ARG, "stokes_apply: needs n >= 3 (n = %d)", prm->n);
+    if ((int64_t)prm->n * prm->n * 5 > INT32_MAX)
+        return set_error(MPBP_ERR_OVERFLOW, "stokes_apply: n = %d too large (5 n^2 > INT32_MAX)", prm->n);
+    FStencilDev P;
+    int rc = make_fstencil(prm, cell, uface, vface, nullptr, &P);
+    if (rc) return rc;
+    const hipStream_t st = as_stream(stream);
+    switch (mode) {
+    case MPBP_SPMV_STORE: return launch_stokes_a(P, prm->d_p, prm->d_div, x, EpiStore{y}, st, fast);
+    case MPBP_SPMV_ADD: return launch_stokes_a(P, prm->d_p, prm->d_div, x, EpiAddLate{z, y}, st, fast);
+    default: return launch_stokes_a(P, prm->d_p, prm->d_div, x, EpiResidLate{z, y}, st, fast);
     }
 }
 

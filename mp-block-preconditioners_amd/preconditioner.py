@@ -82,6 +82,83 @@ class PGStencil:
         return out
 
 
+class StokesOperator:
+    """The system matrix A = [[F, d_p G], [d_div D, 0]] (preconditioner.py:339-341) applied matrix-free: every row of
+    ``A x`` (np.matmul(A, u_vec), apply.py:72; FGMRES's operator) recomputed from the thn tables in one launch
+    (mpbp_stokes_apply), nothing assembled.  numerics "exact": the assembled A's ``matvec`` bit for bit; "fast": the
+    tolerance-mode F rows (within 1e-12 of it; pressure rows unchanged).  The tables are held by address
+    (``update_theta_tables`` is seen without any call); ``set_params`` rewrites the coefficients in place.  One GPU,
+    n >= 3."""
+
+    dtype = torch.float64
+
+    def __init__(self, prm: _lib.StokesParams, tables, numerics: str = "exact"):
+        if numerics not in ("exact", "fast"):
+            raise ValueError("numerics must be 'exact' or 'fast'")
+        if prm.n < 3:
+            raise ValueError("StokesOperator needs n >= 3 (the periodic neighbours coincide below that)")
+        self.prm = prm
+        self.cell, self.uface, self.vface = tables
+        self.numerics = numerics
+
+    @property
+    def shape(self):
+        m = 5 * self.prm.n * self.prm.n
+        return (m, m)
+
+    @property
+    def device(self):
+        return self.cell.device
+
+    def set_params(self, c, d_u, d_p=1.0, d_div=-1.0, xi=None, eta_n=None, eta_s=None):
+        """New coefficients in place (a time step); xi, eta_n, eta_s None: kept."""
+        p = self.prm
+        p.c, p.d_u, p.d_p, p.d_div = float(c), float(d_u), float(d_p), float(d_div)
+        for name, v in (("xi", xi), ("eta_n", eta_n), ("eta_s", eta_s)):
+            if v is not None:
+                setattr(p, name, float(v))
+
+    def matvec(self, x, out=None, mode=_lib.SPMV_STORE, z=None):
+        """y = A x (mode STORE), z + A x (ADD) or z - A x (RESID) on CUDA float64 vectors; out must not be x."""
+        m = self.shape[0]
+        if not (isinstance(x, torch.Tensor) and x.dtype == torch.float64 and x.is_cuda and x.numel() >= m):
+            raise ValueError(f"matvec: x must be a CUDA float64 tensor of at least {m} entries")
+        if out is None:
+            out = torch.empty(m, dtype=torch.float64, device=self.device)
+        elif not (out.dtype == torch.float64 and out.is_cuda and out.numel() >= m):
+            raise ValueError(f"matvec: out must be a CUDA float64 tensor of at least {m} entries")
+        if z is not None and not (z.dtype == torch.float64 and z.is_cuda and z.numel() >= m):
+            raise ValueError(f"matvec: z must be a CUDA float64 tensor of at least {m} entries")
+        flags = int(mode) | (_lib.SPMV_FAST if self.numerics == "fast" else 0)
+        check(lib().mpbp_stokes_apply(ctypes.byref(self.prm), ptr(self.cell), ptr(self.uface), ptr(self.vface), flags,
+                                      ptr(x), ptr(z), ptr(out), stream_handle()))
+        return out
+
+    def apply(self, x, out=None):
+        """y = A x: the operator surface fgmres and print_true_res_norm drive."""
+        return self.matvec(x, out=out)
+
+    def __matmul__(self, other):
+        if isinstance(other, np.ndarray) and other.ndim == 1:
+            return self._host_matvec(other)
+        if isinstance(other, torch.Tensor):
+            return self.matvec(other)
+        return NotImplemented
+
+    def _host_matvec(self, x: np.ndarray) -> np.ndarray:
+        """A @ x for a host vector of exactly 5 n^2 entries, staged as DeviceCSR._host_matvec stages it."""
+        from .solve import _staged_host_call
+        return _staged_host_call(self, x, self.shape[1], self.shape[0], self.device,
+                                 lambda d_in, d_out: self.matvec(d_in, out=d_out))
+
+    def release_staging(self):
+        """Free the host-vector matvec's staging buffers (re-created on demand)."""
+        self._pinned = None
+
+    def __repr__(self):
+        return f"StokesOperator(n={self.prm.n}, numerics={self.numerics!r}, device={self.device})"
+
+
 class MultiphaseBlockPreconditioner:
     def __init__(self, n, xi, eta_n=1.0, eta_s=1.0, device=None):
         if int(n) < 1:
@@ -192,14 +269,25 @@ class MultiphaseBlockPreconditioner:
                 self.assemble(_lib.OP_XI_S if s else _lib.OP_XI_N),
                 self.assemble(_lib.OP_G_S if s else _lib.OP_G_N))
 
-    def get_big_A_matrix(self, c, d_u, d_p: float = 1.0, d_div: float = -1.0):
-        """(A, S, F, D, G) (preconditioner.py:299-349); S (dense exact Schur complement) is None."""
+    def stokes_operator(self, c, d_u, d_p: float = 1.0, d_div: float = -1.0, numerics: str = "exact"):
+        """The matrix-free system matrix (StokesOperator) over this object's thn tables; n >= 3."""
+        if self.n < 3:
+            raise ValueError("stokes_operator needs n >= 3 (the periodic neighbours coincide below that)")
+        return StokesOperator(self._params(c, d_u, d_p, d_div), self.theta_tables(), numerics)
+
+    def get_big_A_matrix(self, c, d_u, d_p: float = 1.0, d_div: float = -1.0, matrix_free_A: bool = False):
+        """(A, S, F, D, G) (preconditioner.py:299-349); S (dense exact Schur complement) is None.  matrix_free_A: A's
+        CSR is never assembled, A is the StokesOperator (n >= 3)."""
         kw = dict(c=c, d_u=d_u, d_p=d_p, d_div=d_div)
-        A = self.assemble(_lib.OP_A, **kw)
+        if matrix_free_A:
+            A = self.stokes_operator(**kw)
+        else:
+            A = self.assemble(_lib.OP_A, **kw)
+            A.row_groups = 5   # [u_n|v_n|u_s|v_s|p] rows over the same cells
         F = self.assemble(_lib.OP_F, **kw)
         D = self.assemble(_lib.OP_D, **kw)
         G = self.assemble(_lib.OP_G, **kw)
-        A.row_groups, F.row_groups, G.row_groups = 5, 4, 4   # [u_n|v_n|u_s|v_s|p] rows over the same cells
+        F.row_groups, G.row_groups = 4, 4
         if self.n >= 3:   # the matrix-free forms (periodic neighbours are distinct from n = 3 on)
             prm, tabs = self._params(**kw), self.theta_tables()
             F.stencil = FStencil(prm, tabs)
@@ -212,9 +300,18 @@ class MultiphaseBlockPreconditioner:
         and coefficients on the same grid): mpbp_stokes_fill into each operator's own arrays, the values a fresh
         get_big_A_matrix(c, d_u, d_p, d_div) holds bit for bit; no allocation, every address kept.  xi, eta_n and eta_s
         are this object's current attributes.  The StokesParams the operators' stencils share are updated in place
-        (a plan's by-value copy is rewritten by ApproxSchurPreconditioner.refresh).  An operator may be None."""
+        (a plan's by-value copy is rewritten by ApproxSchurPreconditioner.refresh).  An operator may be None; A may
+        be a StokesOperator (get_big_A_matrix(matrix_free_A=True)): it holds no values, only its parameters change."""
         cell, uface, vface = self.theta_tables()
         prm = self._params(c, d_u, d_p, d_div)
+        op_A = None
+        if isinstance(A, StokesOperator):
+            op_A, A = A, None
+            if op_A.prm.n != self.n:
+                raise ValueError(f"refill: the StokesOperator is on an n = {op_A.prm.n} grid, not this n = {self.n}")
+            if op_A.cell.data_ptr() != cell.data_ptr():
+                raise ValueError("refill: the StokesOperator reads other thn tables than this object's (tables "
+                                 "replaced by set_theta_tables since it was built; use update_theta_tables)")
         ops = ((A, _lib.OP_A), (F, _lib.OP_F), (D, _lib.OP_D), (G, _lib.OP_G))
         for M, op in ops:   # refuse everything before anything is written
             if M is None:
@@ -235,6 +332,8 @@ class MultiphaseBlockPreconditioner:
             st = getattr(M, "stencil", None)
             if st is not None:
                 ctypes.memmove(ctypes.byref(st.prm), ctypes.byref(prm), ctypes.sizeof(prm))
+        if op_A is not None:
+            ctypes.memmove(ctypes.byref(op_A.prm), ctypes.byref(prm), ctypes.sizeof(prm))
 
     @staticmethod
     def refresh_products(F: DeviceCSR, D: DeviceCSR, G: DeviceCSR, GtG: DeviceCSR, GtFG: DeviceCSR):

@@ -1001,14 +1001,15 @@ def print_true_res_norm(A, b_vec):
 
 
 def solve_with_approx_schur_pc(n, xi, etan, etas, c, d, b_vec, u_vec, inner_F=None, inner_P=None,
-                               tol=1e-8, maxiter=150, verbose=True):
+                               tol=1e-8, maxiter=150, verbose=True, matrix_free_A=False):
     """solve.py:240-286: FGMRES on A with the approximate-commutator preconditioner.
 
+    matrix_free_A: A is never assembled, FGMRES applies it through the StokesOperator (same bits, n >= 3).
     Returns (u_approx, info, residual history) with u_approx a host array.
     """
     from .utils import print_norms
     bp = MultiphaseBlockPreconditioner(n, xi, etan, etas)
-    A, _, F, D, G = bp.get_big_A_matrix(c=c, d_u=d)
+    A, _, F, D, G = bp.get_big_A_matrix(c=c, d_u=d, matrix_free_A=matrix_free_A)
     pc = ApproxSchurPreconditioner(F, D, G, inner_F=inner_F, inner_P=inner_P)
     b = torch.from_numpy(np.ascontiguousarray(b_vec, dtype=np.float64)).to(pc.device)
     hist = []
@@ -1024,7 +1025,7 @@ def solve_with_approx_schur_pc(n, xi, etan, etas, c, d, b_vec, u_vec, inner_F=No
 def solve_without_pc(n, A, b_vec, u_vec, tol=1e-8, maxiter=100, verbose=True):
     """solve.py:202-208: FGMRES on A without a preconditioner (x0 = 0), then the error norms.
 
-    A is the DeviceCSR from get_big_A_matrix; returns (u_approx, info, residual history)."""
+    A is the DeviceCSR (or the StokesOperator) from get_big_A_matrix; returns (u_approx, info, residual history)."""
     from .utils import print_norms
     b = torch.from_numpy(np.ascontiguousarray(b_vec, dtype=np.float64)).to(A.device)
     hist = []

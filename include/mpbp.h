@@ -13,7 +13,8 @@
  *   mpbp_spgemm_*         Gt_G = np.matmul(mD, G), Gt_F_G = (mD F) G          solve.py:246-249
  *   mpbp_spmv             b_approx = np.matmul(A, u_vec)                      apply.py:72
  *                         A @ xk in the FGMRES residual callback              solve.py:166
- *   mpbp_stokes_apply     the same products with A's rows recomputed from thn (nothing assembled)
+ *   mpbp_stokes_apply     the same products with A's rows recomputed from thn (nothing assembled);
+ *                         mpbp_stokes_apply_part: one rank's rows of it under the grid-row partition
  *   mpbp_jacobi_*         Jacobi(A, b, N, x)                                  solve.py:149-159
  *   mpbp_cheb_*           inner Chebyshev sweeps (BASELINE.json configs[3])
  *   mpbp_f_stencil_*      the F products / sweeps above with F's rows recomputed from thn
@@ -501,6 +502,22 @@ int mpbp_gtg_stencil_cheb_solve(const mpbp_stokes_params* prm, const double* cel
  * nothing is launched then. */
 int mpbp_stokes_apply(const mpbp_stokes_params* prm, const double* cell, const double* uface, const double* vface,
                       int32_t mode, const double* x, const double* z, double* y, void* stream);
+/* The same operator on one rank's rows of a grid-row partition (multi-GPU FGMRES's operator).  part == NULL or
+ * part->halo == 0: mpbp_stokes_apply itself (the same launch, the same bits).  Otherwise the rank owns grid rows
+ * [r0, r0 + rows) of each of the 5 fields [u_n | v_n | u_s | v_s | p] and
+ *   x: 5 (rows + 2 halo) n doubles in the owned + ghost layout -- the owned rows field-major, (f * rows + lr) * n + c,
+ *      then `halo` rows above (grid rows r0 - halo .. r0 - 1, periodic) of every field, field-major, then `halo` rows
+ *      below of every field (RowPartition.ext_rows(5, halo)); the caller fills the ghost rows (a halo exchange);
+ *   y, z: 5 rows n doubles, the owned rows alone, (f * rows + lr) * n + c -- A's product has no ghost rows.
+ * which: 0 all owned rows, 1 rows 1 .. rows - 2 (no ghost row read; nothing to do when rows <= 2: MPBP_OK, no launch),
+ * 2 rows 0 and rows - 1.  The three thn tables are the GLOBAL n x n tables on every rank.  Every row performs the one-
+ * GPU entry's operations in its order: the rows of mpbp_stokes_apply's result bit for bit, in both numerics.  One
+ * launch, no allocation or synchronisation (capturable).  MPBP_ERR_ARG, nothing launched: what mpbp_stokes_apply
+ * refuses; which == 3 or ext != 0 (no ghost output), which outside 0..2; rows < 1, r0 < 0, r0 + rows > n,
+ * halo > rows; oh other than 0 or halo.  MPBP_ERR_OVERFLOW: 5 n^2 or 5 (rows + 2 halo) n > INT32_MAX. */
+int mpbp_stokes_apply_part(const mpbp_stokes_params* prm, const double* cell, const double* uface,
+                           const double* vface, const mpbp_row_part* part, int32_t mode, const double* x,
+                           const double* z, double* y, void* stream);
 
 /* ---- kernel choices ------------------------------------------------------------------------------ */
 /* Which kernel form runs each step.  Every choice gives the same results as every other (bit-identical), except

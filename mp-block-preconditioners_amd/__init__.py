@@ -8,6 +8,7 @@ from .mg import FIELDS_PRESSURE, FIELDS_VELOCITY, Multigrid
 from .preconditioner import MultiphaseBlockPreconditioner, StokesOperator, thn, ths
 from .solve import (ApproxSchurPreconditioner, InnerSolver, fgmres, print_true_res_norm,
                     solve_with_approx_schur_pc, solve_without_pc)
+from .distributed import DistributedStokesOperator
 from .utils import (fill_sol_and_RHS_vecs, manufactured_problem, manufactured_problem_constant, max_norm, print_norms, weighted_L1,
                     weighted_L2)
 
@@ -17,4 +18,5 @@ __all__ = [
     "ApproxSchurPreconditioner", "InnerSolver", "fgmres", "print_true_res_norm",
     "solve_with_approx_schur_pc", "solve_without_pc", "fill_sol_and_RHS_vecs", "manufactured_problem", "manufactured_problem_constant", "max_norm",
     "print_norms", "weighted_L1", "weighted_L2", "Multigrid", "FIELDS_VELOCITY", "FIELDS_PRESSURE",
+    "DistributedStokesOperator",
 ]

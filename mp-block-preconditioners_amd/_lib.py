@@ -211,6 +211,7 @@ _SIGNATURES = {
                                   _P, _P, _P, _P], c_int),
     "mpbp_pg_stencil_spmv": ([POINTER(StokesParams), _P, POINTER(RowPart), c_int32, c_int32, _P, _P, _P, _P], c_int),
     "mpbp_stokes_apply": ([POINTER(StokesParams), _P, _P, _P, c_int32, _P, _P, _P, _P], c_int),
+    "mpbp_stokes_apply_part": ([POINTER(StokesParams), _P, _P, _P, POINTER(RowPart), c_int32, _P, _P, _P, _P], c_int),
     "mpbp_gtg_stencil_jacobi_step": ([POINTER(StokesParams), _P, POINTER(RowPart), _P, _P, _P, _P, _P], c_int),
     "mpbp_gtg_stencil_cheb_step": ([POINTER(StokesParams), _P, POINTER(RowPart), _P, _P, c_double, c_double, _P, _P,
                                     _P, _P], c_int),

@@ -4089,13 +4089,22 @@ struct GStencilDev : PGDev {
 // each entry d_div * (inv * avg) as the assembly forms it (phase_D_row's value scaled by d_div).  With FStencilFast
 // the velocity rows start from the regrouped rows (rows4); the G products and the pressure row are the exact ones
 // (explicit operations, the file is built without contraction), so pressure rows agree bit for bit in both modes.
-// One GPU, whole-grid layouts, n >= 3.
-template <class FS>
+// n >= 3.  PART = false: one GPU, whole-grid layouts.  PART = true: the rank's rows of a row partition (FS's r0, L, h,
+// which = 0 / 1 / 2): x in the 5-field owned + ghost layout (ext_row), y and z the owned rows alone (A's product has
+// no ghost rows); the thn tables, cell_pre, the column wrap and the EDGE test stay in global grid coordinates, so a
+// row's operations and their order are the one-GPU instance's.
+template <class FS, bool PART = false>
 struct StokesADev : FS {
     double d_p, d_div, inv, minv;   // inv = 1.0 / dx, minv = -1.0 / dx as phase_D_row / phase_G_row evaluate them
     static constexpr int NF = 5, NOUT = 5;
-    __device__ int32_t xrow(int f, int gr) const { return (f * this->n + this->wrap(gr)) * this->n; }
-    __device__ int32_t out_row(int o, int lr, int gc) const { return (o * this->n + lr) * this->n + gc; }
+    __device__ int32_t xrow(int f, int gr) const {
+        if constexpr (PART) return ext_row(5, f, gr - this->r0, this->L, this->h, this->n);
+        else return (f * this->n + this->wrap(gr)) * this->n;
+    }
+    __device__ int32_t out_row(int o, int lr, int gc) const {
+        if constexpr (PART) return (o * this->L + lr) * this->n + gc;
+        else return (o * this->n + lr) * this->n + gc;
+    }
     // velocity row o's two G products added to acc: the wrapped neighbour sorts last
     template <bool EDGE, class TA, class XA>
     __device__ double add_g(double acc, int o, int gr, int gc, const TA& ta, const XA& xa) const {
@@ -4160,12 +4169,12 @@ struct StokesADev : FS {
     }
 };
 
-template <class Epi>
+template <bool PART, class Epi>
 int launch_stokes_a(const FStencilDev& P, double d_p, double d_div, const double* x, Epi epi, hipStream_t st,
                     bool fast) {
     const double dx = 1.0 / P.n;
     auto go = [&](const auto& Q) {
-        using S = StokesADev<std::decay_t<decltype(Q)>>;
+        using S = StokesADev<std::decay_t<decltype(Q)>, PART>;
         const S A{Q, d_p, d_div, 1.0 / dx, -1.0 / dx};
         const int64_t chunks = march_chunks(A, KO().march_rows, march_capacity<k_march<S, XPlain, Epi, BNone>>());
         if (chunks == 0) return (int)MPBP_OK;
@@ -6918,9 +6927,9 @@ int mpbp_stokes_apply(const mpbp_stokes_params* prm, const double* cell, const d
     if (rc) return rc;
     const hipStream_t st = as_stream(stream);
     switch (mode) {
-    case MPBP_SPMV_STORE: return launch_stokes_a(P, prm->d_p, prm->d_div, x, EpiStore{y}, st, fast);
-    case MPBP_SPMV_ADD: return launch_stokes_a(P, prm->d_p, prm->d_div, x, EpiAddLate{z, y}, st, fast);
-    default: return launch_stokes_a(P, prm->d_p, prm->d_div, x, EpiResidLate{z, y}, st, fast);
+    case MPBP_SPMV_STORE: return launch_stokes_a<false>(P, prm->d_p, prm->d_div, x, EpiStore{y}, st, fast);
+    case MPBP_SPMV_ADD: return launch_stokes_a<false>(P, prm->d_p, prm->d_div, x, EpiAddLate{z, y}, st, fast);
+    default: return launch_stokes_a<false>(P, prm->d_p, prm->d_div, x, EpiResidLate{z, y}, st, fast);
     }
 }
 
@@ -9171,4 +9180,51 @@ int mpbp_mg_solve(const mpbp_mg* mg, const double* b, const double* sub, double*
     return mg_solve(mg, f, b, x_out, sub, as_stream(stream));
 }
 
+// The matrix-free system matrix on one rank's rows of the row partition (StokesADev<FS, true>).  Kept last in the
+// file: its kernel instances follow every other kernel in the code object.
+int mpbp_stokes_apply_part(const mpbp_stokes_params* prm, const double* cell, const double* uface,
+                           const double* vface, const mpbp_row_part* part, int32_t mode, const double* x,
+                           const double* z, double* y, void* stream) {
+    if (!part || part->halo <= 0) return mpbp_stokes_apply(prm, cell, uface, vface, mode, x, z, y, stream);
+    // mpbp_stokes_apply's refusals, then the partition's; every one before the first HIP call
+    if (!prm || !cell || !uface || !vface)
+        return set_error(MPBP_ERR_ARG, "stokes_apply: needs the parameters and the three thn tables");
+    const bool fast = (mode & MPBP_SPMV_FAST) != 0;
+    mode &= ~MPBP_SPMV_FAST;
+    if (mode != MPBP_SPMV_STORE && mode != MPBP_SPMV_ADD && mode != MPBP_SPMV_RESID)
+        return set_error(MPBP_ERR_ARG, "stokes_apply: unknown mode %d", mode);
+    if (!x || !y || x == y || (mode != MPBP_SPMV_STORE && !z))
+        return set_error(MPBP_ERR_ARG, "stokes_apply: bad vectors (x, y distinct and non-null; z for ADD / RESID)");
+    if (prm->n < 3) return set_error(MPBP_ERR_ARG, "stokes_apply: needs n >= 3 (n = %d)", prm->n);
+    if ((int64_t)prm->n * prm->n * 5 > INT32_MAX)
+        return set_error(MPBP_ERR_OVERFLOW, "stokes_apply: n = %d too large (5 n^2 > INT32_MAX)", prm->n);
+    // A's output is the owned rows alone: no ghost rows computed (which = 3, ext), no output ghost depth of its own
+    if (part->which < 0 || part->which > 2 || part->ext != 0)
+        return set_error(MPBP_ERR_ARG, "stokes_apply_part: which = %d, ext = %d (which must be 0, 1 or 2 and ext 0: "
+                         "A's output has no ghost layout)", part->which, part->ext);
+    if (part->rows < 1 || part->r0 < 0 || (int64_t)part->r0 + part->rows > prm->n || part->halo > part->rows)
+        return set_error(MPBP_ERR_ARG, "stokes_apply_part: bad row partition (r0 = %d, rows = %d, halo = %d, n = %d)",
+                         part->r0, part->rows, part->halo, prm->n);
+    if (part->oh != 0 && part->oh != part->halo)
+        return set_error(MPBP_ERR_ARG, "stokes_apply_part: oh = %d must be 0 or the halo depth %d", part->oh, part->halo);
+    if (((int64_t)part->rows + 2 * (int64_t)part->halo) * prm->n * 5 > INT32_MAX)
+        return set_error(MPBP_ERR_OVERFLOW, "stokes_apply_part: 5 (rows + 2 halo) n > INT32_MAX");
+    FStencilDev P;
+    int rc = make_fstencil(prm, cell, uface, vface, part, &P);
+    if (rc) return rc;
+    const hipStream_t st = as_stream(stream);
+    switch (mode) {
+    case MPBP_SPMV_STORE: return launch_stokes_a<true>(P, prm->d_p, prm->d_div, x, EpiStore{y}, st, fast);
+    case MPBP_SPMV_ADD: return launch_stokes_a<true>(P, prm->d_p, prm->d_div, x, EpiAddLate{z, y}, st, fast);
+    default: return launch_stokes_a<true>(P, prm->d_p, prm->d_div, x, EpiResidLate{z, y}, st, fast);
+    }
+}
+
 }  // extern "C"
+
+// Placement pad.  The code object's .text follows its metadata and .rodata, so adding kernels moves every kernel's
+// offset within its 4 KB page.  With the partitioned A instances added, .text went from page offset 0x800 to 0x900
+// and bench.py's apply -- byte-identical kernels -- measured 0.9-1.0 % slower in alternating runs (6980-7006 against
+// 7059-7068 applies/s); these 0xF00 read-only bytes put .text back at 0x800 (7045-7078).  DESIGN.md section 4f.
+// Re-derive or drop it when the kernel set changes (llvm-objdump -h on the unbundled gfx950 code object).
+extern "C" __device__ __attribute__((used)) const char mpbp_text_pad[0xF00] = {1};

@@ -979,6 +979,110 @@ class DistributedMatrix:
         return self.part.owned_rows(self.nfields)
 
 
+class DistributedStokesOperator:
+    """The row-partitioned system matrix applied matrix-free: DistributedMatrix's surface and schedule with every owned
+    row of ``A x`` recomputed from the thn tables (mpbp_stokes_apply_part) -- no row of A assembled, extracted,
+    renumbered or planned on any rank.
+
+    op: a StokesOperator (``bp.stokes_operator(c, d_u)``), held by reference: ``bp.update_theta_tables(...)`` and
+    ``op.set_params(...)`` are seen by the next apply with no rebuild (there is nothing to refill).  Numerics are
+    ``op.numerics``: "exact" gives the rows of the assembled A's product (DistributedMatrix.apply, and the one-GPU
+    StokesOperator) bit for bit, "fast" the one-GPU fast operator's rows bit for bit.
+
+    apply(x) takes and returns the rank's owned entries (5 fields, owned grid rows [r0, r1), field-major): x is copied
+    into the 5-field ext buffer, the ghost rows (h = 1) are exchanged -- RCCL on a communicator of this object's own
+    (overlap=True: on the halo's side stream, across the interior rows' launch) or the host-staged HaloExchanger
+    (gloo) -- while the rows 1 .. L-2 (no ghost read) run, and the first and last owned grid rows run after the
+    exchange.  Unpartitioned (world 1 without self_halo) apply is ``op.matvec``.
+
+    Needs n >= 3.  Every rank holds the three GLOBAL thn tables (3 n^2 doubles: 100 MB at 2048^2) -- the tables are
+    not partitioned."""
+
+    nfields = 5
+    h = 1
+
+    def __init__(self, op, group=None, halo: str = "auto", overlap: bool = True, self_halo: bool = False):
+        from .preconditioner import StokesOperator
+        if not isinstance(op, StokesOperator):
+            raise TypeError("DistributedStokesOperator needs a StokesOperator (MultiphaseBlockPreconditioner.stokes_operator)")
+        if halo not in ("auto", "rccl", "torch"):
+            raise ValueError("halo must be 'auto', 'rccl' or 'torch'")
+        dist, world, rank, backend = _dist_info(group)
+        n = int(op.prm.n)
+        if n < 3:
+            raise ValueError("DistributedStokesOperator needs n >= 3")
+        self.op = op
+        self.part = part = RowPartition(n, world, rank, ghosts=bool(self_halo))
+        self.partitioned = part.ghosts
+        self.halo_impl = halo if halo != "auto" else ("rccl" if backend == "nccl" else "torch")
+        self.n_own = part.n_owned(5)
+        self.n_ext = part.n_ext(5, self.h)
+        self.shape = (self.n_own, self.n_own)
+        self._rccl = self._ex = self.xe = None
+        if self.partitioned:
+            self.xe = torch.zeros(self.n_ext, dtype=torch.float64, device=op.device)
+            self._parts = tuple(_lib.RowPart(part.r0, part.L, self.h, which, 0, 0) for which in (0, 1, 2))
+            if self.halo_impl == "rccl":
+                # its own communicator, as DistributedMatrix: eager exchanges on the halo object's side stream are never
+                # mixed with the preconditioner's in-order ones on one communicator
+                self._rccl = RcclHalo(part, 1, 1, group, overlap=False, share=False)
+                self.kind = self._rccl.add_kind(part, 5, self.h, overlap=overlap)
+            else:
+                self._ex = HaloExchanger(part, 5, self.h, op.device, group)
+
+    @property
+    def device(self):
+        return self.op.device
+
+    @property
+    def numerics(self):
+        return self.op.numerics
+
+    def _launch(self, which: int, out, mode=_lib.SPMV_STORE, z=None):
+        op = self.op
+        flags = int(mode) | (_lib.SPMV_FAST if op.numerics == "fast" else 0)
+        check(lib().mpbp_stokes_apply_part(ctypes.byref(op.prm), ptr(op.cell), ptr(op.uface), ptr(op.vface),
+                                           ctypes.byref(self._parts[which]), flags, ptr(self.xe), ptr(z), ptr(out),
+                                           stream_handle()))
+
+    def apply(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        assert x.is_cuda and x.dtype == torch.float64 and x.numel() == self.n_own
+        if out is None:
+            out = torch.empty(self.n_own, dtype=torch.float64, device=x.device)
+        if not self.partitioned:
+            return self.op.matvec(x, out=out)
+        assert out.is_cuda and out.dtype == torch.float64 and out.numel() == self.n_own
+        self.xe[: self.n_own].copy_(x)
+        st = stream_handle()
+        if self._rccl is not None:
+            lib().mpbp_halo_exchange(self._rccl.handle, self.kind, ptr(self.xe), _lib.HALO_BEGIN, st)
+        else:
+            self._ex.begin(self.xe)
+        self._launch(1, out)          # rows 1 .. L-2: no ghost row read (nothing launched when L <= 2)
+        if self._rccl is not None:
+            lib().mpbp_halo_exchange(self._rccl.handle, self.kind, ptr(self.xe), _lib.HALO_END, st)
+        else:
+            self._ex.end(self.xe)
+        self._launch(2, out)          # the first and last owned grid rows
+        if self._rccl is not None:
+            self._rccl.check()
+        return out
+
+    matvec = apply
+
+    def close(self):
+        if self._rccl is not None:
+            self._rccl.close()
+            self._rccl = None
+
+    def local_to_global_rows(self):
+        return self.part.owned_rows(5)
+
+    def __repr__(self):
+        return (f"DistributedStokesOperator(n={self.part.n}, rows=[{self.part.r0}, {self.part.r1}), "
+                f"numerics={self.numerics!r}, halo={self.halo_impl if self.partitioned else None!r})")
+
+
 def _csr_vstack(A: DeviceCSR, B: DeviceCSR) -> DeviceCSR:
     """The rows of A, then the rows of B (same column count), as one CSR."""
     rp = torch.cat([A.row_ptr[:-1], B.row_ptr + A.nnz])
@@ -1104,7 +1208,8 @@ class DistributedSchurPreconditioner(PlanProfiling):
                 del D1
             del Fs
         else:
-            _, _, F, D, G = bp.get_big_A_matrix(**akw)
+            # (the preconditioner reads F, D and G alone: A's own CSR is not assembled to be dropped)
+            _, _, F, D, G = bp.get_big_A_matrix(matrix_free_A=n >= 3, **akw)
             _stamp("assemble_global")
             GtG, GtFG = bp.commutator_products(F, D, G)
             _stamp("commutator_products")
@@ -1405,21 +1510,28 @@ class DistributedSchurPreconditioner(PlanProfiling):
 
 
 def solve_distributed(n, xi, etan, etas, c=1.0, d=-1.0, b_vec=None, inner_F=None, inner_P=None, tol=1e-8,
-                      maxiter=150, restrt=None, group=None, self_halo=False, keep_operators=False, **pc_kw):
+                      maxiter=150, restrt=None, group=None, self_halo=False, keep_operators=False,
+                      matrix_free_A=False, **pc_kw):
     """solve.py:240-286 over a row partition (one rank per GPU): FGMRES (solve.fgmres over `group`) on the partitioned
     operator A (DistributedMatrix) with the partitioned approximate-commutator preconditioner
     (DistributedSchurPreconditioner).  b_vec: the global right-hand side on the host (default: the manufactured problem
     of solve.py:52-80).  The solve is the one-GPU solve's, bit for bit (reproducible inner products).  Returns a dict:
     x_local (this rank's rows of the iterate, CUDA), rows (their global ids), info, residuals, A, M.  Unless
     keep_operators, A and M are closed before the return (their RCCL communicators destroyed here, at the same point on
-    every rank, also when the solve raises -- not whenever the garbage collector of each rank gets to them)."""
+    every rank, also when the solve raises -- not whenever the garbage collector of each rank gets to them).
+    matrix_free_A: the operator is a DistributedStokesOperator over ``bp.stokes_operator(c, d)`` (exact numerics) -- no
+    row of A is assembled on any rank, at any world size (self_halo included; n >= 3); its rows are the assembled ones
+    bit for bit, so the iterates and the residual history are the same."""
     import torch.distributed as dist
     from .preconditioner import MultiphaseBlockPreconditioner
     from .solve import fgmres
     from .utils import manufactured_problem
     bp = MultiphaseBlockPreconditioner(n, xi, etan, etas)
     world = dist.get_world_size(group)
-    if world > 1:   # rank-local: this rank's rows of A only
+    if matrix_free_A:
+        dA = DistributedStokesOperator(bp.stokes_operator(c, d), group=group, self_halo=self_halo,
+                                       halo=pc_kw.get("halo", "auto"))
+    elif world > 1:   # rank-local: this rank's rows of A only
         part = RowPartition(n, world, dist.get_rank(group))
         rows = torch.from_numpy(part.owned_rows(5).astype(np.int32)).cuda()
         dA = DistributedMatrix(bp.assemble_rows(_lib.OP_A, rows, c=c, d_u=d), n, 5, group=group, owned_rows=True,

@@ -23,7 +23,7 @@ def main():
             cur = {"name": m.group(1)}
             rows.append(cur)
             continue
-        m = re.search(r"remark: +(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs): (\d+)", line)
+        m = re.search(r"remark: +(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs|LDS Size \[bytes/block\]): (\d+)", line)
         if m and cur is not None:
             cur[m.group(1).split()[0]] = int(m.group(2))
     demangled = subprocess.run(["c++filt"], input="\n".join(r["name"] for r in rows),
@@ -33,7 +33,7 @@ def main():
         d = d.replace("(anonymous namespace)::", "")
         if keys and not any(k in d for k in keys):
             continue
-        print(f"{r.get('VGPRs', '?'):>4} vgpr {r.get('SGPRs', '?'):>4} sgpr {r.get('ScratchSize', '?'):>4} scratch occ {r.get('Occupancy', '?')}  {d[:150]}")
+        print(f"{r.get('VGPRs', '?'):>4} vgpr {r.get('SGPRs', '?'):>4} sgpr {r.get('ScratchSize', '?'):>4} scratch {r.get('LDS', '?'):>6} lds occ {r.get('Occupancy', '?')}  {d[:150]}")
 
 
 if __name__ == "__main__":

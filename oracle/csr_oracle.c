@@ -4,7 +4,8 @@
  *
  * Every sum runs over a CSR row in storage order, left to right, starting from
  * 0.0, with no fused multiply-add (built with -ffp-contract=off): the GPU
- * kernels in mp-block-preconditioners_amd/csrc/mpbp.hip perform the same IEEE
+ * kernels in mp-block-preconditioners_amd/csrc (mpbp.hip and the *.inc
+ * fragments it includes) perform the same IEEE
  * operations in the same order, so results compare bit for bit.
  *
  *   spmv            b_approx = A @ u_vec                         apply.py:72

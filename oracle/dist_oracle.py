@@ -34,7 +34,7 @@ def extract_rows(M, rows, colmap, ncols_local):
 
 
 def _inner(M, diag, inner: Inner, b, ex, x_bufs, dst, sub=None):
-    """Mirror of mpbp.hip inner_solve on ext vectors (torch CPU tensors, shared with numpy)."""
+    """Mirror of schur_inner.inc inner_solve on ext vectors (torch CPU tensors, shared with numpy)."""
     K = inner.sweeps
     ping, pong, dvec = x_bufs
     nown = M.shape[0]

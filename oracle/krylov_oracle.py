@@ -34,7 +34,7 @@ FOLDS = 3
 
 
 def rd_sigmas(bound: float, ntot: int) -> list[float]:
-    """The 3 extractors for terms |t| <= bound over ntot terms (mpbp.hip rd_sigmas)."""
+    """The 3 extractors for terms |t| <= bound over ntot terms (krylov.inc rd_sigmas)."""
     if not math.isfinite(bound):
         return [float("nan")] * FOLDS
     if not bound > 0.0:
@@ -51,7 +51,7 @@ def rd_sigmas(bound: float, ntot: int) -> list[float]:
 
 
 def fold_terms(t: np.ndarray, sig) -> np.ndarray:
-    """(FOLDS, len(t)): the pre-rounded parts q_f of every term (mpbp.hip rd_fold)."""
+    """(FOLDS, len(t)): the pre-rounded parts q_f of every term (krylov.inc rd_fold)."""
     r = np.asarray(t, dtype=np.float64).copy()
     q = np.zeros((FOLDS, r.size))
     for f, s in enumerate(sig):
@@ -88,7 +88,7 @@ def rdot(V, w, ntot=None, bv=None, bw=None) -> np.ndarray:
 
 
 def gs_update(V, k, h, w) -> np.ndarray:
-    """w - sum_i V[i] h[i], the products added in order i = 0 .. k-1 from 0.0 (mpbp.hip k_gs_update)."""
+    """w - sum_i V[i] h[i], the products added in order i = 0 .. k-1 from 0.0 (krylov.inc k_gs_update)."""
     a = np.zeros_like(np.asarray(w, dtype=np.float64))
     for i in range(k):
         a = a + V[i] * h[i]
@@ -96,7 +96,7 @@ def gs_update(V, k, h, w) -> np.ndarray:
 
 
 def update_bound(bw: float, bv, h, k: int) -> float:
-    """The a-priori bound on |w - V^T h| the fused CGS2 pass takes its extractors from (mpbp.hip k_gs_update_rdot):
+    """The a-priori bound on |w - V^T h| the fused CGS2 pass takes its extractors from (krylov.inc k_gs_update_rdot):
     (max|w| + sum_i bv[i] |h[i]|, added in order) (1 + 2^-40)."""
     b = float(bw)
     for i in range(k):
@@ -116,7 +116,7 @@ def rdot2_folds(V, u, w, ntot, bv, bu: float, bw: float) -> np.ndarray:
 
 
 def dcgs2_coeffs(j: int, acc, bw: float):
-    """mpbp.hip k_dcgs2_coeffs: (hu[0..j], hw[0..j], P = [r, 1/r, c, bound of u_{j+1}]) in the kernel's order."""
+    """krylov.inc k_dcgs2_coeffs: (hu[0..j], hw[0..j], P = [r, 1/r, c, bound of u_{j+1}]) in the kernel's order."""
     k = j + 1
     a = np.asarray(acc, dtype=np.float64)
     hu = [(float(a[3 * i]) + float(a[3 * i + 1])) + float(a[3 * i + 2]) for i in range(k)]
@@ -137,7 +137,7 @@ def dcgs2_coeffs(j: int, acc, bw: float):
 
 
 def dcgs2_update(V: np.ndarray, j: int, hu, hw, P, w, upd_w=True):
-    """mpbp.hip k_dcgs2_update on a (>= j + 2) x n basis, in place: V[j] <- (V[j] - sum_i V[i] s_i) / r,
+    """krylov.inc k_dcgs2_update on a (>= j + 2) x n basis, in place: V[j] <- (V[j] - sum_i V[i] s_i) / r,
     V[j + 1] <- ((w - sum_i V[i] z_i) - V[j] c) / r, the sums over i < j in order from 0.0."""
     su = np.zeros(V.shape[1])
     sw = np.zeros(V.shape[1])

@@ -150,3 +150,19 @@ def test_kernel_options_block_lifetime_and_reentry():
         assert _lib.kernel_opts().march_rows == 7
     assert not any(x is o for x in _lib._INSTALLED)
     assert _lib.kernel_opts().march_rows == base.march_rows
+
+
+def test_every_fragment_is_included_exactly_once():
+    """csrc/mpbp.hip is the one translation unit and the csrc/*.inc fragments are its text: every fragment is included
+    exactly once, by mpbp.hip alone, and mpbp.hip includes nothing from csrc that is not there.  A text check."""
+    csrc = os.path.join(ROOT, "mp-block-preconditioners_amd", "csrc")
+    fragments = sorted(f for f in os.listdir(csrc) if f.endswith(".inc"))
+    assert fragments
+    quoted = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
+    with open(os.path.join(csrc, "mpbp.hip")) as f:
+        included = [i for i in quoted.findall(f.read()) if i != "mpbp.h"]   # mpbp.h: include/, found by -I
+    assert sorted(included) == fragments, (sorted(set(fragments) - set(included)), sorted(set(included) - set(fragments)),
+                                           sorted(i for i in set(included) if included.count(i) > 1))
+    for name in fragments:   # no fragment pulls in another: the order is mpbp.hip's alone
+        with open(os.path.join(csrc, name)) as f:
+            assert not quoted.findall(f.read()), name

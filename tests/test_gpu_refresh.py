@@ -384,7 +384,7 @@ def test_preconditioner_refresh_csr_layout():
     _refresh_walk(16, PAIRS[1], layout="csr")
 
 
-# n = 96: every fused launch of the apply is taken (csrc/mpbp.hip: k_fsolve from n = 72, k_ftile 76, k_gtg_solve 78 for
+# n = 96: every fused launch of the apply is taken (csrc/: k_fsolve from n = 72, k_ftile 76, k_gtg_solve 78 for
 # four sweeps, k_fpre / k_gal1 / k_gal1p 72, k_gtg_level0 78, the level-1 <PRO> ascents 80) -- the kernels that read the
 # plan's by-value f_prm, the Chebyshev intervals and the multigrid levels a refresh rewrites
 N_FUSED = 96

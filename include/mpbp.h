@@ -228,7 +228,8 @@ typedef struct mpbp_mg {
     mpbp_gather_fn gather;
     /* optional (tr_nfields > 0): the transfers' field kinds (MPBP_MG_CELL / NODE along y and x per field, as
      * mpbp_mg_transfer_fill) and level 0's grid size: the whole-grid levels' restriction and prolongation are then
-     * applied matrix-free, their weights and columns recomputed per row in the CSR form's order (same bits) */
+     * applied matrix-free, their weights and columns recomputed per row in the CSR form's order (same bits).  Level l's
+     * size is tr_n0 >> l; an odd level's transfers are mpbp_mg_transfer_any_fill's */
     int32_t tr_nfields;
     int32_t tr_n0;
     int32_t tr_ky[8];
@@ -343,6 +344,11 @@ int mpbp_exclusive_scan(const int32_t* row_nnz, int32_t* row_ptr, int64_t n, int
 int mpbp_spgemm_count(const mpbp_csr* A, const mpbp_csr* B, int32_t* row_nnz, void* stream);
 int mpbp_spgemm_fill(const mpbp_csr* A, const mpbp_csr* B, double alpha, const int32_t* row_ptr,
                      int32_t* col_idx, double* val, void* stream);
+/* The wide forms: output rows up to 128 entries (MPBP_ERR_OVERFLOW beyond) -- the Galerkin rows of a hierarchy with an
+ * odd level reach 86.  Same traversal, same bits. */
+int mpbp_spgemm_count_wide(const mpbp_csr* A, const mpbp_csr* B, int32_t* row_nnz, void* stream);
+int mpbp_spgemm_fill_wide(const mpbp_csr* A, const mpbp_csr* B, double alpha, const int32_t* row_ptr,
+                          int32_t* col_idx, double* val, void* stream);
 /* Values-only products into a pattern that is already known (a time step's new coefficients on the same grid): only
  * C->val is written, C's row_ptr / col_idx are read.  One wavefront per output row, lane t owning the row's entry t;
  * every entry receives its products in mpbp_spgemm_fill's order, so the values are that builder's bit for bit (composed
@@ -358,6 +364,11 @@ int mpbp_spgemm_fill(const mpbp_csr* A, const mpbp_csr* B, double alpha, const i
 int mpbp_spgemm_refill(const mpbp_csr* A, const mpbp_csr* B, double alpha, const mpbp_csr* C, void* stream);
 int mpbp_triple_refill(const mpbp_csr* X, const mpbp_csr* Y, const mpbp_csr* Z, int32_t assoc, double alpha_inner,
                        double alpha_outer, const mpbp_csr* C, void* stream);
+/* The wide forms: output rows up to 128 entries, two per lane (MPBP_ERR_OVERFLOW "output row wider than 128"); a
+ * triple's inner rows stay within 64 ("inner row wider than 64").  Same traversal, same bits, same other errors. */
+int mpbp_spgemm_refill_wide(const mpbp_csr* A, const mpbp_csr* B, double alpha, const mpbp_csr* C, void* stream);
+int mpbp_triple_refill_wide(const mpbp_csr* X, const mpbp_csr* Y, const mpbp_csr* Z, int32_t assoc, double alpha_inner,
+                            double alpha_outer, const mpbp_csr* C, void* stream);
 
 /* ---- Gt_F_G in the 13-point diamond layout ---------------------------------------------------- */
 /* Gt_F_G = ((-D) F) G (solve.py:246-249) couples each pressure cell with the 13 cells |dr| + |dc| <= 2 (n >= 5).
@@ -603,6 +614,18 @@ int mpbp_mg_transfer_rows_count(int32_t n, int32_t nfields, const int32_t* kinds
                                 int32_t nrows, int32_t* row_nnz, void* stream);
 int mpbp_mg_transfer_rows_fill(int32_t n, int32_t nfields, const int32_t* kinds, int32_t which, const int32_t* rows,
                                int32_t nrows, const int32_t* row_ptr, int32_t* col_idx, double* val, void* stream);
+/* The any-size rule (Multigrid(coarsen="any")): the same P / R for a fine size n >= 5 of either parity coarsened to
+ * nc = n / 2 (floor).  Fine point f is interpolated linearly from the two coarse points around num / den on the
+ * periodic grid -- node-centred num = f nc, den = n; cell-centred num = (2 f + 1) nc - n, den = 2 n (negative at f = 0:
+ * floor towards -inf): i0 = floor(num / den), rem = num - i0 den; rem == 0: the one entry (i0 mod nc, 1.0), else
+ * (i0 mod nc, (den - rem) / den) and ((i0 + 1) mod nc, rem / den), each weight one division of two exact integers.
+ * 1D lists sorted by index (P: 1-2 entries, R = P^T: 3-5, the same quotients); 2D weights yw * xw, columns sorted.
+ * For even n these are mpbp_mg_transfer_*'s matrices bit for bit.  Inside mpbp_mg_solve a hierarchy that names its
+ * field kinds (tr_nfields > 0) applies an odd level's transfers matrix-free from the same lists (n <= 32768).  Setup. */
+int mpbp_mg_transfer_any_count(int32_t n, int32_t nfields, const int32_t* kinds, int32_t which, int32_t* row_nnz,
+                               void* stream);
+int mpbp_mg_transfer_any_fill(int32_t n, int32_t nfields, const int32_t* kinds, int32_t which, const int32_t* row_ptr,
+                              int32_t* col_idx, double* val, void* stream);
 /* x_out = mg->cycles V-cycles for levels[0].A x = b from x = 0 (sub - x when sub != NULL).  Graph-capturable.
  * Row-partitioned hierarchies (part_levels > 0): b, sub, x_out hold the rank's owned rows of level 0. */
 int mpbp_mg_solve(const mpbp_mg* mg, const double* b, const double* sub, double* x_out, void* stream);

@@ -183,6 +183,11 @@ _SIGNATURES = {
     "mpbp_spgemm_count": ([POINTER(Csr), POINTER(Csr), _P, _P], c_int),
     "mpbp_spgemm_fill": ([POINTER(Csr), POINTER(Csr), c_double, _P, _P, _P, _P], c_int),
     "mpbp_spgemm_refill": ([POINTER(Csr), POINTER(Csr), c_double, POINTER(Csr), _P], c_int),
+    "mpbp_spgemm_count_wide": ([POINTER(Csr), POINTER(Csr), _P, _P], c_int),
+    "mpbp_spgemm_fill_wide": ([POINTER(Csr), POINTER(Csr), c_double, _P, _P, _P, _P], c_int),
+    "mpbp_spgemm_refill_wide": ([POINTER(Csr), POINTER(Csr), c_double, POINTER(Csr), _P], c_int),
+    "mpbp_triple_refill_wide": ([POINTER(Csr), POINTER(Csr), POINTER(Csr), c_int32, c_double, c_double, POINTER(Csr),
+                                 _P], c_int),
     "mpbp_triple_refill": ([POINTER(Csr), POINTER(Csr), POINTER(Csr), c_int32, c_double, c_double, POINTER(Csr), _P],
                            c_int),
     "mpbp_plan_row_blocks": ([_P, c_int32, c_int32, _P, c_int64], c_int64),
@@ -263,6 +268,8 @@ _SIGNATURES = {
     "mpbp_q13_spmv": ([c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p], c_int),
     "mpbp_mg_transfer_count": ([c_int32, c_int32, _P, c_int32, _P, _P], c_int),
     "mpbp_mg_transfer_fill": ([c_int32, c_int32, _P, c_int32, _P, _P, _P, _P], c_int),
+    "mpbp_mg_transfer_any_count": ([c_int32, c_int32, _P, c_int32, _P, _P], c_int),
+    "mpbp_mg_transfer_any_fill": ([c_int32, c_int32, _P, c_int32, _P, _P, _P, _P], c_int),
     "mpbp_mg_transfer_rows_count": ([c_int32, c_int32, _P, c_int32, _P, c_int32, _P, _P], c_int),
     "mpbp_mg_transfer_rows_fill": ([c_int32, c_int32, _P, c_int32, _P, c_int32, _P, _P, _P, _P], c_int),
     "mpbp_mg_solve": ([POINTER(Mg), _P, _P, _P, _P], c_int),

@@ -329,14 +329,16 @@ def csr_from_row_nnz(row_nnz: torch.Tensor, shape, device):
     return row_ptr, col, val
 
 
-def spgemm(A: DeviceCSR, B: DeviceCSR, alpha: float = 1.0) -> DeviceCSR:
-    """alpha * A @ B keeping every structural product (solve.py:246-249 use np.matmul)."""
+def spgemm(A: DeviceCSR, B: DeviceCSR, alpha: float = 1.0, wide: bool = False) -> DeviceCSR:
+    """alpha * A @ B keeping every structural product (solve.py:246-249 use np.matmul).  Output rows of at most 64
+    entries; wide: at most 128 (mpbp_spgemm_*_wide, the same rows bit for bit)."""
     if A.shape[1] != B.shape[0]:
         raise ValueError(f"shape mismatch {A.shape} @ {B.shape}")
+    count, fill = ((lib().mpbp_spgemm_count_wide, lib().mpbp_spgemm_fill_wide) if wide else
+                   (lib().mpbp_spgemm_count, lib().mpbp_spgemm_fill))
     row_nnz = torch.empty(A.shape[0], dtype=torch.int32, device=A.device)
-    check(lib().mpbp_spgemm_count(ctypes.byref(A.cstruct()), ctypes.byref(B.cstruct()), ptr(row_nnz),
-                                  stream_handle()))
+    check(count(ctypes.byref(A.cstruct()), ctypes.byref(B.cstruct()), ptr(row_nnz), stream_handle()))
     rp, ci, va = csr_from_row_nnz(row_nnz, (A.shape[0], B.shape[1]), A.device)
-    check(lib().mpbp_spgemm_fill(ctypes.byref(A.cstruct()), ctypes.byref(B.cstruct()), float(alpha), ptr(rp),
-                                 ptr(ci), ptr(va), stream_handle()))
+    check(fill(ctypes.byref(A.cstruct()), ctypes.byref(B.cstruct()), float(alpha), ptr(rp), ptr(ci), ptr(va),
+               stream_handle()))
     return DeviceCSR(rp, ci, va, (A.shape[0], B.shape[1]))

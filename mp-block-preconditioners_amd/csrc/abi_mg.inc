@@ -78,6 +78,46 @@ int mpbp_mg_transfer_rows_fill(int32_t n, int32_t nfields, const int32_t* kinds,
     return MPBP_OK;
 }
 
+// the any-size rule's arguments: n >= 5 of either parity (nc = n / 2 >= 2)
+static int mg_fields_any(int32_t n, int32_t nfields, const int32_t* kinds, MgFields* F) {
+    if (n < 5 || nfields < 1 || nfields > 8 || !kinds)
+        return set_error(MPBP_ERR_ARG, "mg_transfer_any: need n >= 5 and 1..8 fields");
+    F->nfields = nfields;
+    for (int f = 0; f < nfields; ++f) {
+        F->ky[f] = kinds[2 * f];
+        F->kx[f] = kinds[2 * f + 1];
+        if ((F->ky[f] != MPBP_MG_CELL && F->ky[f] != MPBP_MG_NODE) || (F->kx[f] != MPBP_MG_CELL && F->kx[f] != MPBP_MG_NODE))
+            return set_error(MPBP_ERR_ARG, "mg_transfer_any: field kinds must be MPBP_MG_CELL or MPBP_MG_NODE");
+    }
+    if ((int64_t)nfields * n * n > INT32_MAX) return set_error(MPBP_ERR_ARG, "mg_transfer_any: too many rows");
+    return MPBP_OK;
+}
+
+int mpbp_mg_transfer_any_count(int32_t n, int32_t nfields, const int32_t* kinds, int32_t which, int32_t* row_nnz,
+                               void* stream) {
+    MgFields F;
+    const int rc = mg_fields_any(n, nfields, kinds, &F);
+    if (rc) return rc;
+    if (!row_nnz || (which != MPBP_MG_P && which != MPBP_MG_R)) return set_error(MPBP_ERR_ARG, "mg_transfer_any: bad args");
+    const int64_t rows = mg_rows(n, nfields, which);
+    k_mg_transfer_any<<<grid_for(rows), kBlock, 0, as_stream(stream)>>>(F, n, which, rows, nullptr, row_nnz, nullptr, nullptr);
+    MPBP_HIP(hipGetLastError());
+    return MPBP_OK;
+}
+
+int mpbp_mg_transfer_any_fill(int32_t n, int32_t nfields, const int32_t* kinds, int32_t which, const int32_t* row_ptr,
+                              int32_t* col_idx, double* val, void* stream) {
+    MgFields F;
+    const int rc = mg_fields_any(n, nfields, kinds, &F);
+    if (rc) return rc;
+    if (!row_ptr || !col_idx || !val || (which != MPBP_MG_P && which != MPBP_MG_R))
+        return set_error(MPBP_ERR_ARG, "mg_transfer_any: bad args");
+    const int64_t rows = mg_rows(n, nfields, which);
+    k_mg_transfer_any<<<grid_for(rows), kBlock, 0, as_stream(stream)>>>(F, n, which, rows, row_ptr, nullptr, col_idx, val);
+    MPBP_HIP(hipGetLastError());
+    return MPBP_OK;
+}
+
 int mpbp_mg_accel_coeffs(double rho, int32_t K, double* omega, double* mu) {
     if (K < 1 || K > 64 || !omega || !mu || !(rho > 0.0) || !(rho < 1.0))
         return set_error(MPBP_ERR_ARG, "mg_accel_coeffs: need 1 <= K <= 64 and 0 < rho < 1");

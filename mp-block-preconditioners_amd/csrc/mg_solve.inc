@@ -68,23 +68,31 @@ MgFields mg_fields(const mpbp_mg* m) {
 inline MgDiv mg_div(int32_t nr) { return MgDiv{divu((uint32_t)nr * (uint32_t)nr), divu((uint32_t)nr)}; }
 // Level l's restriction (which = MPBP_MG_R) or prolongation (MPBP_MG_P) matrix-free when the hierarchy names its
 // field kinds and the level is whole-grid (not row-partitioned); 1: launched, 0: not applicable.
+// Level l's size is tr_n0 >> l under either coarsening rule (floor halving).  An even level takes the 2:1 lists
+// (k_mg_transfer_spmv), an odd one -- coarsen="any" hierarchies only -- the any-size lists (k_mg_transfer_any_spmv).
 template <class Epi>
 int mg_transfer_mf(const mpbp_mg* m, int l, int32_t which, int32_t nrows, const double* x, Epi epi, hipStream_t st) {
     const int32_t n = m->tr_n0 >> l, nr = which == MPBP_MG_P ? n : n / 2;
-    k_mg_transfer_spmv<Epi><<<grid_for(nrows), kBlock, 0, st>>>(mg_fields(m), mg_div(nr), n, which, nrows, x, epi);
+    if (n & 1)
+        k_mg_transfer_any_spmv<Epi><<<grid_for(nrows), kBlock, 0, st>>>(mg_fields(m), mg_div(nr), n, which, nrows, x, epi);
+    else
+        k_mg_transfer_spmv<Epi><<<grid_for(nrows), kBlock, 0, st>>>(mg_fields(m), mg_div(nr), n, which, nrows, x, epi);
     MPBP_HIP(hipGetLastError());
     return MPBP_OK;
 }
+inline bool mg_level_even(const mpbp_mg* m, int l) { return ((m->tr_n0 >> l) & 1) == 0; }
 inline bool use_mf_transfer(const mpbp_mg* m, int l) {
-    return KO().mg_mf_transfer && m->tr_nfields > 0 && m->tr_nfields <= 8 && l >= m->part_levels && (m->tr_n0 >> l) >= 4 &&
-           ((m->tr_n0 >> l) << l) == m->tr_n0;
+    const int32_t n = m->tr_n0 >> l;
+    return KO().mg_mf_transfer && m->tr_nfields > 0 && m->tr_nfields <= 8 && l >= m->part_levels && n >= 4 &&
+           (mg_level_even(m, l) || (n >= 5 && n <= kMgAnyMaxN));
 }
 // Kernel option mg_fuse_small (k_grp_rr): level l >= 1 of a hierarchy held whole on this GPU (one GPU, or a level every
 // rank replicates), its operator on k_csr_grp rows, its transfers matrix-free with the level sizes the transfers imply,
-// the coarse level at most kRrMaxCoarse rows.
+// the coarse level at most kRrMaxCoarse rows.  An even level only: k_grp_rr builds the 2:1 restriction lists (<= 16 fine
+// rows per coarse row).
 bool mg_small_ok(const mpbp_mg* m, int l, const OpPair& o) {
     if (!KO().mg_fuse_small || l < 1 || l < m->part_levels || l + 1 >= m->nlevels || !o.in.grp || !o.in.csr ||
-        o.in.gal || !o.bd.empty || !use_mf_transfer(m, l))
+        o.in.gal || !o.bd.empty || !use_mf_transfer(m, l) || !mg_level_even(m, l))
         return false;
     const int64_t n = m->tr_n0 >> l, rows = (int64_t)m->tr_nfields * n * n;
     const mpbp_csr& A = *o.in.csr;
@@ -306,7 +314,7 @@ bool mg_gal_ok(const mpbp_mg* m, const MgFine& f) {
     const MgGal g{m, o, f.r, f.d};
     if (m->part_levels == 0)
         return o.which == 0 && f.op.bd.empty && !f.halo && !o.stencil->halo && use_mf_transfer(m, 0) &&
-               (KO().mg_galerkin_mf == 1 || gal_fused_ok(g));
+               mg_level_even(m, 0) && (KO().mg_galerkin_mf == 1 || gal_fused_ok(g));
     return f.halo && o.stencil->halo && m->tr_nfields > 0 && m->tr_n0 == o.stencil->f_prm.n && gal_fused_ok(g);
 }
 

@@ -467,9 +467,11 @@ struct Csr {
 };
 
 constexpr int kSpgemmMaxW = 64;
+constexpr int kSpgemmWideW = 128;   // the wide forms' output rows (mpbp_*_wide): Galerkin rows below an odd level reach 86
 
 // Row r of A*B: first-touch order over (A row order, B row order), then sorted by column.
 // Same operation order as oracle/csr_oracle.c:row_product.
+template <int W = kSpgemmMaxW>
 __device__ int spgemm_row(const Csr A, const Csr B, int32_t r, int32_t* cols, double* vals) {
     int m = 0;
     for (int32_t ka = A.rp[r]; ka < A.rp[r + 1]; ++ka) {
@@ -483,7 +485,7 @@ __device__ int spgemm_row(const Csr A, const Csr B, int32_t r, int32_t* cols, do
             if (t < m) {
                 vals[t] += v;
             } else {
-                if (m == kSpgemmMaxW) return -1;
+                if (m == W) return -1;
                 cols[m] = j;
                 vals[m] = v;
                 ++m;
@@ -501,23 +503,25 @@ __device__ int spgemm_row(const Csr A, const Csr B, int32_t r, int32_t* cols, do
     return m;
 }
 
+template <int W = kSpgemmMaxW>
 __global__ void k_spgemm_count(Csr A, Csr B, int32_t nrows, int32_t* row_nnz, int* overflow) {
     const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nrows) return;
-    int32_t cols[kSpgemmMaxW];
-    double vals[kSpgemmMaxW];
-    const int m = spgemm_row(A, B, r, cols, vals);
+    int32_t cols[W];
+    double vals[W];
+    const int m = spgemm_row<W>(A, B, r, cols, vals);
     if (m < 0) { atomicAdd(overflow, 1); row_nnz[r] = 0; }
     else row_nnz[r] = m;
 }
 
+template <int W = kSpgemmMaxW>
 __global__ void k_spgemm_fill(Csr A, Csr B, int32_t nrows, double alpha, const int32_t* crp,
                               int32_t* cci, double* cva) {
     const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nrows) return;
-    int32_t cols[kSpgemmMaxW];
-    double vals[kSpgemmMaxW];
-    const int m = spgemm_row(A, B, r, cols, vals);
+    int32_t cols[W];
+    double vals[W];
+    const int m = spgemm_row<W>(A, B, r, cols, vals);
     const int32_t base = crp[r];
     for (int k = 0; k < m; ++k) {
         cci[base + k] = cols[k];
@@ -542,6 +546,7 @@ struct RCsr {
 constexpr int kRefillLong = 1;      // an output or inner row holds more than kSpgemmMaxW entries
 constexpr int kRefillMissing = 2;   // a product's column is not in C's row
 constexpr int kRefillIndex = 4;     // a row extent or column index outside its array
+constexpr int kRefillWide = 8;      // the wide form: an output row holds more than kSpgemmWideW entries
 
 // lane `src` (wave-uniform) of v
 __device__ inline int32_t lane_get(int32_t v, int src) { return __builtin_amdgcn_readlane(v, src); }
@@ -584,6 +589,42 @@ __device__ inline void wave_feed(WaveRow& w, int lane, int32_t j, double v, int&
     }
 }
 
+// The wide form's output row (mpbp_*_refill_wide): lane t holds entries t and t + 64 of a row of m <= kSpgemmWideW
+// entries.  Its pattern is fixed (never APPEND), and an entry still receives its products one by one in the traversal's
+// order, so the sums are WaveRow's.
+struct WaveRow2 {
+    int32_t col, col2;
+    double val, val2;
+    bool hit, hit2;
+    int m;
+};
+// the product (j, v) added to the entry of column j; false on every lane when the row lacks that column
+__device__ inline bool wave_take(WaveRow& w, int lane, int32_t j, double v) {
+    const bool mine = lane < w.m && w.col == j;
+    if (mine) {
+        w.val = w.hit ? w.val + v : v;
+        w.hit = true;
+    }
+    return mine;
+}
+__device__ inline bool wave_take(WaveRow2& w, int lane, int32_t j, double v) {
+    const bool mine = lane < w.m && w.col == j, mine2 = lane + 64 < w.m && w.col2 == j;
+    if (mine) {
+        w.val = w.hit ? w.val + v : v;
+        w.hit = true;
+    }
+    if (mine2) {
+        w.val2 = w.hit2 ? w.val2 + v : v;
+        w.hit2 = true;
+    }
+    return mine || mine2;
+}
+template <bool APPEND>
+__device__ inline void wave_feed(WaveRow2& w, int lane, int32_t j, double v, int& err) {
+    static_assert(!APPEND, "a wide row's pattern is fixed");
+    if (!__builtin_amdgcn_ballot_w64(wave_take(w, lane, j, v))) err |= kRefillMissing;
+}
+
 __device__ inline int64_t lane_get(int64_t v, int src) {
     return ((int64_t)__builtin_amdgcn_readlane((int32_t)(v >> 32), src) << 32) |
            (uint32_t)__builtin_amdgcn_readlane((int32_t)v, src);
@@ -608,8 +649,8 @@ __device__ inline double lane_push(double v, int dst) {
 // order: spgemm_row's traversal of one A row.  The rows' extents, then their entries 64 at a time, are loaded one per
 // lane and the products formed there, so no row costs a dependent memory round trip of its own; only the accumulation
 // walks the products one by one.
-template <bool APPEND>
-__device__ inline void wave_feed_rows(WaveRow& w, int lane, int n, int32_t k, double a, const RCsr& B, int& err) {
+template <bool APPEND, class Row>
+__device__ inline void wave_feed_rows(Row& w, int lane, int n, int32_t k, double a, const RCsr& B, int& err) {
     int32_t b0 = 0, len = 0;
     bool bad = false;
     if (lane < n) {
@@ -643,8 +684,8 @@ __device__ inline void wave_feed_rows(WaveRow& w, int lane, int n, int32_t k, do
 }
 
 // row r of A B in spgemm_row's traversal order
-template <bool APPEND>
-__device__ inline void wave_feed_product(WaveRow& w, int lane, const RCsr& A, const RCsr& B, int32_t r, int& err) {
+template <bool APPEND, class Row>
+__device__ inline void wave_feed_product(Row& w, int lane, const RCsr& A, const RCsr& B, int32_t r, int& err) {
     int32_t a0, a1;
     if (r < 0 || r >= A.nrows || !row_extent(A, r, a0, a1)) { err |= kRefillIndex; return; }
     for (int64_t ca = a0; ca < a1; ca += 64) {
@@ -671,7 +712,8 @@ constexpr int kRefillPair = 0, kRefillLeft = 1, kRefillRight = 2;
 //             order (the order spgemm_fill stored it in)
 //      right: C = alpha_outer X (alpha_inner Y Z)    -- inner row k per entry (r, k) of X; its columns are distinct,
 //             so each goes to another output entry and their order within the row reaches no sum
-template <int MODE>
+//      WIDE:  output rows up to kSpgemmWideW entries, two per lane (WaveRow2); inner rows stay within a wave's 64
+template <int MODE, bool WIDE = false>
 __global__ void __launch_bounds__(kBlock) k_refill(RCsr X, RCsr Y, RCsr Z, double alpha_inner, double alpha_outer,
                                                    RCsr C, double* cva, int* errs) {
     const int lane = threadIdx.x & 63;
@@ -680,10 +722,13 @@ __global__ void __launch_bounds__(kBlock) k_refill(RCsr X, RCsr Y, RCsr Z, doubl
     int err = 0;
     int32_t c0, c1;
     if (!row_extent(C, r, c0, c1)) err |= kRefillIndex;
-    else if (c1 - c0 > kSpgemmMaxW) err |= kRefillLong;
+    else if (c1 - c0 > (WIDE ? kSpgemmWideW : kSpgemmMaxW)) err |= WIDE ? kRefillWide : kRefillLong;
     if (!err) {
-        WaveRow w{0, 0.0, false, c1 - c0};
+        typename std::conditional<WIDE, WaveRow2, WaveRow>::type w{};
+        w.m = c1 - c0;
         if (lane < w.m) w.col = C.ci[c0 + lane];
+        if constexpr (WIDE)
+            if (lane + 64 < w.m) w.col2 = C.ci[c0 + 64 + lane];
         if (MODE == kRefillPair) {
             wave_feed_product<false>(w, lane, X, Y, r, err);
         } else if (MODE == kRefillLeft) {
@@ -704,19 +749,28 @@ __global__ void __launch_bounds__(kBlock) k_refill(RCsr X, RCsr Y, RCsr Z, doubl
                     wave_feed_product<true>(t, lane, Y, Z, lane_get(xk, i), err);
                     const double xt = lane_get(xv, i) * (alpha_inner * t.val);
                     bool got = false;
+                    int taken = 0;   // WIDE: a lane may receive two of the inner row's products (its two entries)
                     for (int s = 0; s < t.m; ++s) {
                         const int32_t j = lane_get(t.col, s);
                         const double v = lane_get(xt, s);
-                        if (lane < w.m && w.col == j) {
+                        if constexpr (WIDE) {
+                            taken += __builtin_amdgcn_ballot_w64(wave_take(w, lane, j, v)) ? 1 : 0;
+                        } else if (lane < w.m && w.col == j) {
                             w.val = w.hit ? w.val + v : v;
                             w.hit = got = true;
                         }
                     }
-                    if (__popcll((unsigned long long)__builtin_amdgcn_ballot_w64(got)) != t.m) err |= kRefillMissing;
+                    if constexpr (WIDE) {
+                        if (taken != t.m) err |= kRefillMissing;
+                    } else if (__popcll((unsigned long long)__builtin_amdgcn_ballot_w64(got)) != t.m) {
+                        err |= kRefillMissing;
+                    }
                 }
             }
         }
         if (!err && lane < w.m) cva[c0 + lane] = w.hit ? alpha_outer * w.val : 0.0;
+        if constexpr (WIDE)
+            if (!err && lane + 64 < w.m) cva[c0 + 64 + lane] = w.hit2 ? alpha_outer * w.val2 : 0.0;
     }
     if (err && lane == 0) {
         atomicOr(&errs[0], err);
@@ -974,6 +1028,132 @@ __global__ void k_mg_transfer(MgFields F, int32_t n, int32_t which, int64_t nrow
             va[k] = yw[a] * xw[b];
             ++k;
         }
+}
+
+// ---- coarsening of any fine size (mpbp_mg_transfer_any_*, Multigrid(coarsen="any")) ----
+// Fine size nf >= 5 (odd or even) coarsens to nc = nf / 2 (floor).  Fine point f sits at the coarse coordinate
+// t_f = num / den, from integers only -- node-centred: num = f nc, den = nf; cell-centred: num = (2 f + 1) nc - nf,
+// den = 2 nf (negative at f = 0: the floor is towards -inf) -- and is interpolated linearly from the coarse points
+// i0 = floor(t_f) and i0 + 1 on the periodic grid: weights (den - rem) / den and rem / den with rem = num - i0 den, each
+// ONE division of two exactly representable integers (never 1 - w), a single entry of weight 1.0 when rem == 0.  For even
+// nf these are mg_p1d's lists, indices and bits.  R = P^T takes the same quotients: coarse i collects the (unwrapped)
+// fine points with |num - i den| < den, at most 5 of them, distinct modulo nf since nf >= 5.
+// I: int64_t (the stored builders) or int32_t (the matrix-free rows: nf <= kMgAnyMaxN keeps every product below 2^31).
+constexpr int kMgAnyMaxN = 32768;
+template <class I>
+__device__ inline I mg_floor_div(I a, I b) {   // b > 0
+    const I q = a / b;
+    return (a - q * b) < 0 ? q - 1 : q;
+}
+template <class I>
+__device__ inline I mg_any_num(int kind, I nf, I nc, I f) {
+    return kind == MPBP_MG_NODE ? f * nc : (2 * f + 1) * nc - nf;
+}
+// P's 1D list for fine index f (fine size nf): 1 or 2 entries, in increasing index order
+template <class I>
+__device__ inline int mg_p1d_any(int kind, int nf_, int f, int* idx, double* w) {
+    const I nf = nf_, nc = nf_ / 2, den = kind == MPBP_MG_NODE ? nf : 2 * nf;
+    const I num = mg_any_num<I>(kind, nf, nc, (I)f);
+    const I i0 = mg_floor_div<I>(num, den), rem = num - i0 * den;
+    I a = i0 % nc;
+    if (a < 0) a += nc;
+    if (rem == 0) {
+        idx[0] = (int)a;
+        w[0] = 1.0;
+        return 1;
+    }
+    const I b = a + 1 == nc ? 0 : a + 1;
+    const double wa = (double)(den - rem) / (double)den, wb = (double)rem / (double)den;
+    const bool bfirst = b < a;
+    idx[0] = (int)(bfirst ? b : a);  w[0] = bfirst ? wb : wa;
+    idx[1] = (int)(bfirst ? a : b);  w[1] = bfirst ? wa : wb;
+    return 2;
+}
+// R's 1D list for coarse index i (fine size nf) = column i of P: 3 to 5 entries, in increasing index order
+template <class I>
+__device__ inline int mg_r1d_any(int kind, int nf_, int i, int* idx, double* w) {
+    const I nf = nf_, nc = nf_ / 2, den = kind == MPBP_MG_NODE ? nf : 2 * nf;
+    // the first fine index with num > (i - 1) den -- node: f nc > (i - 1) nf; cell: (2 f + 1) nc > (2 i - 1) nf -- is one
+    // past the floor of the bound; the window's members follow it consecutively (num grows with f), in [-3, nf + 3)
+    const I f0 = 1 + (kind == MPBP_MG_NODE ? mg_floor_div<I>(((I)i - 1) * nf, nc)
+                                           : mg_floor_div<I>((2 * (I)i - 1) * nf - nc, 2 * nc));
+    int m = 0;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {   // (constant indices keep the lists in registers)
+        const I f = f0 + j;
+        const I val = mg_any_num<I>(kind, nf, nc, f) - (I)i * den;   // (t_f - i) den > -den
+        const bool in = val < den;
+        idx[j] = (int)(f < 0 ? f + nf : f >= nf ? f - nf : f);
+        w[j] = (double)(val < 0 ? den + val : den - val) / (double)den;
+        m += in ? 1 : 0;
+    }
+    sort_pairs<5>(m, idx, w);
+    return m;
+}
+
+struct MgRowAny {
+    int my, mx, nk, off;
+    int yi[5], xi[5];
+    double yw[5], xw[5];
+};
+// y = op(T x) for the any-size P or R, matrix-free: each row rebuilds mg_p1d_any / mg_r1d_any's lists, the products
+// and the order k_mg_transfer_any stores, so the sums are the stored CSR's SpMV bit for bit (as k_mg_transfer_spmv
+// is to k_mg_transfer).  n <= kMgAnyMaxN.
+template <class Epi>
+__global__ void __launch_bounds__(kBlock) k_mg_transfer_any_spmv(MgFields F, MgDiv dv, int32_t n, int32_t which,
+                                                                 int32_t nrows, const double* __restrict__ x, Epi epi) {
+    const int32_t row = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
+    if (row >= nrows) return;
+    const typename Epi::P pe = epi.pre(row);
+    const int nc = n / 2;
+    const int nr = which == MPBP_MG_P ? n : nc, nk = which == MPBP_MG_P ? nc : n;
+    const uint32_t per = (uint32_t)nr * (uint32_t)nr;
+    const int fld = (int)divu((uint32_t)row, dv.per);
+    const uint32_t cell = (uint32_t)row - (uint32_t)fld * per;
+    const int r = (int)divu(cell, dv.nr), c = (int)(cell - (uint32_t)r * (uint32_t)nr);
+    MgRowAny T;
+    T.my = which == MPBP_MG_P ? mg_p1d_any<int32_t>(F.ky[fld], n, r, T.yi, T.yw) : mg_r1d_any<int32_t>(F.ky[fld], n, r, T.yi, T.yw);
+    T.mx = which == MPBP_MG_P ? mg_p1d_any<int32_t>(F.kx[fld], n, c, T.xi, T.xw) : mg_r1d_any<int32_t>(F.kx[fld], n, c, T.xi, T.xw);
+    const int off = fld * nk * nk;
+    double acc = 0.0;
+#pragma unroll
+    for (int a = 0; a < 5; ++a)   // (constant trip counts keep the lists in registers)
+#pragma unroll
+        for (int b = 0; b < 5; ++b)
+            if (a < T.my && b < T.mx) acc += (T.yw[a] * T.xw[b]) * x[off + T.yi[a] * nk + T.xi[b]];
+    epi(row, acc, pe);
+}
+
+// The stored form: rows of P (which = MPBP_MG_P, rows = fine unknowns) or R = P^T (rows = coarse unknowns) of the
+// n x n fine grid, n >= 5; row_nnz set: count only.
+__global__ void k_mg_transfer_any(MgFields F, int32_t n, int32_t which, int64_t nrows, const int32_t* rp,
+                                  int32_t* row_nnz, int32_t* ci, double* va) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= nrows) return;
+    const int nc = n / 2;
+    const int nr = which == MPBP_MG_P ? n : nc;       // grid size of the rows' level
+    const int nk = which == MPBP_MG_P ? nc : n;       // ... and of the columns' level
+    const int64_t per = (int64_t)nr * nr;
+    const int fld = (int)(row / per);
+    const int64_t cell = row - fld * per;
+    const int r = (int)(cell / nr), c = (int)(cell % nr);
+    int yi[5], xi[5];
+    double yw[5], xw[5];
+    const int my = which == MPBP_MG_P ? mg_p1d_any<int64_t>(F.ky[fld], n, r, yi, yw) : mg_r1d_any<int64_t>(F.ky[fld], n, r, yi, yw);
+    const int mx = which == MPBP_MG_P ? mg_p1d_any<int64_t>(F.kx[fld], n, c, xi, xw) : mg_r1d_any<int64_t>(F.kx[fld], n, c, xi, xw);
+    if (row_nnz) {
+        row_nnz[row] = my * mx;
+        return;
+    }
+    const int64_t off = (int64_t)fld * nk * nk;
+    int32_t k = rp[row];
+    for (int a = 0; a < 5; ++a)
+        for (int b = 0; b < 5; ++b)
+            if (a < my && b < mx) {
+                ci[k] = (int32_t)(off + (int64_t)yi[a] * nk + xi[b]);
+                va[k] = yw[a] * xw[b];
+                ++k;
+            }
 }
 
 // ================================================================== SpMV ====
@@ -5588,6 +5768,44 @@ void cheb_coeffs(double lmin, double lmax, int sweeps, double* c1, double* c2) {
 
 }  // namespace
 
+// C = alpha A B's two passes with output rows up to W entries (mpbp_spgemm_count / _fill and their wide forms)
+namespace {
+template <int W>
+int spgemm_count(const mpbp_csr* A, const mpbp_csr* B, int32_t* row_nnz, void* stream) {
+    int rc = check_csr(A);
+    if (!rc) rc = check_csr(B);
+    if (rc) return rc;
+    if (A->ncols != B->nrows) return set_error(MPBP_ERR_ARG, "spgemm: shape mismatch");
+    int* d_over = nullptr;
+    MPBP_HIP(hipMalloc(&d_over, sizeof(int)));
+    hipError_t e = hipMemsetAsync(d_over, 0, sizeof(int), as_stream(stream));
+    if (e == hipSuccess) {
+        k_spgemm_count<W><<<grid_for(A->nrows), kBlock, 0, as_stream(stream)>>>(to_csr(A), to_csr(B), A->nrows,
+                                                                             row_nnz, d_over);
+        e = hipGetLastError();
+    }
+    int h = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, d_over, sizeof(int), hipMemcpyDeviceToHost, as_stream(stream));
+    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
+    (void)hipFree(d_over);
+    if (e != hipSuccess) return set_error(MPBP_ERR_HIP, "spgemm_count: %s", hipGetErrorString(e));
+    if (h) return set_error(MPBP_ERR_OVERFLOW, "spgemm: %d rows wider than %d", h, W);
+    return MPBP_OK;
+}
+
+template <int W>
+int spgemm_fill(const mpbp_csr* A, const mpbp_csr* B, double alpha, const int32_t* row_ptr, int32_t* col_idx,
+                double* val, void* stream) {
+    int rc = check_csr(A);
+    if (!rc) rc = check_csr(B);
+    if (rc) return rc;
+    k_spgemm_fill<W><<<grid_for(A->nrows), kBlock, 0, as_stream(stream)>>>(to_csr(A), to_csr(B), A->nrows, alpha,
+                                                                        row_ptr, col_idx, val);
+    MPBP_HIP(hipGetLastError());
+    return MPBP_OK;
+}
+}  // namespace
+
 // ================================================================ C ABI ====
 extern "C" {
 
@@ -5802,44 +6020,27 @@ int mpbp_exclusive_scan(const int32_t* row_nnz, int32_t* row_ptr, int64_t n, int
 }
 
 int mpbp_spgemm_count(const mpbp_csr* A, const mpbp_csr* B, int32_t* row_nnz, void* stream) {
-    int rc = check_csr(A);
-    if (!rc) rc = check_csr(B);
-    if (rc) return rc;
-    if (A->ncols != B->nrows) return set_error(MPBP_ERR_ARG, "spgemm: shape mismatch");
-    int* d_over = nullptr;
-    MPBP_HIP(hipMalloc(&d_over, sizeof(int)));
-    hipError_t e = hipMemsetAsync(d_over, 0, sizeof(int), as_stream(stream));
-    if (e == hipSuccess) {
-        k_spgemm_count<<<grid_for(A->nrows), kBlock, 0, as_stream(stream)>>>(to_csr(A), to_csr(B), A->nrows,
-                                                                          row_nnz, d_over);
-        e = hipGetLastError();
-    }
-    int h = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, d_over, sizeof(int), hipMemcpyDeviceToHost, as_stream(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
-    (void)hipFree(d_over);
-    if (e != hipSuccess) return set_error(MPBP_ERR_HIP, "spgemm_count: %s", hipGetErrorString(e));
-    if (h) return set_error(MPBP_ERR_OVERFLOW, "spgemm: %d rows wider than %d", h, kSpgemmMaxW);
-    return MPBP_OK;
+    return spgemm_count<kSpgemmMaxW>(A, B, row_nnz, stream);
 }
-
 int mpbp_spgemm_fill(const mpbp_csr* A, const mpbp_csr* B, double alpha, const int32_t* row_ptr,
                      int32_t* col_idx, double* val, void* stream) {
-    int rc = check_csr(A);
-    if (!rc) rc = check_csr(B);
-    if (rc) return rc;
-    k_spgemm_fill<<<grid_for(A->nrows), kBlock, 0, as_stream(stream)>>>(to_csr(A), to_csr(B), A->nrows, alpha,
-                                                                     row_ptr, col_idx, val);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
+    return spgemm_fill<kSpgemmMaxW>(A, B, alpha, row_ptr, col_idx, val, stream);
+}
+int mpbp_spgemm_count_wide(const mpbp_csr* A, const mpbp_csr* B, int32_t* row_nnz, void* stream) {
+    return spgemm_count<kSpgemmWideW>(A, B, row_nnz, stream);
+}
+int mpbp_spgemm_fill_wide(const mpbp_csr* A, const mpbp_csr* B, double alpha, const int32_t* row_ptr,
+                          int32_t* col_idx, double* val, void* stream) {
+    return spgemm_fill<kSpgemmWideW>(A, B, alpha, row_ptr, col_idx, val, stream);
 }
 
 namespace {
 inline RCsr to_rcsr(const mpbp_csr* A) { return RCsr{A->row_ptr, A->col_idx, A->val, A->nrows, A->ncols, A->nnz}; }
 
-// launches k_refill<MODE> over C's rows, waits and turns the kernel's flags into a return code
+// launches k_refill<MODE> (wide: its two-entries-per-lane form) over C's rows, waits and turns the kernel's flags into
+// a return code
 int run_refill(const char* who, int mode, const mpbp_csr* X, const mpbp_csr* Y, const mpbp_csr* Z, double alpha_inner,
-               double alpha_outer, const mpbp_csr* C, void* stream) {
+               double alpha_outer, const mpbp_csr* C, void* stream, bool wide = false) {
     if (C->nrows == 0) return MPBP_OK;
     hipStream_t st = as_stream(stream);
     int* d_err = nullptr;
@@ -5849,7 +6050,10 @@ int run_refill(const char* who, int mode, const mpbp_csr* X, const mpbp_csr* Y, 
         const unsigned grid = (unsigned)(((int64_t)C->nrows + kBlock / 64 - 1) / (kBlock / 64));
         double* cval = const_cast<double*>(C->val);   // the one array a refill writes
         const RCsr x = to_rcsr(X), y = to_rcsr(Y), z = Z ? to_rcsr(Z) : RCsr{nullptr, nullptr, nullptr, 0, 0, 0};
-        if (mode == kRefillPair) k_refill<kRefillPair><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
+        if (wide && mode == kRefillPair) k_refill<kRefillPair, true><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
+        else if (wide && mode == kRefillLeft) k_refill<kRefillLeft, true><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
+        else if (wide) k_refill<kRefillRight, true><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
+        else if (mode == kRefillPair) k_refill<kRefillPair><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
         else if (mode == kRefillLeft) k_refill<kRefillLeft><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
         else k_refill<kRefillRight><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
         e = hipGetLastError();
@@ -5860,37 +6064,55 @@ int run_refill(const char* who, int mode, const mpbp_csr* X, const mpbp_csr* Y, 
     (void)hipFree(d_err);
     if (e != hipSuccess) return set_error(MPBP_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     if (h[0] & kRefillIndex) return set_error(MPBP_ERR_ARG, "%s: %d rows hold a row extent or column index out of range", who, h[1]);
+    if (h[0] & kRefillWide)
+        return set_error(MPBP_ERR_OVERFLOW, "%s: %d rows have an output row wider than %d", who, h[1], kSpgemmWideW);
     if (h[0] & kRefillLong)
-        return set_error(MPBP_ERR_OVERFLOW, "%s: %d rows have an output or inner row wider than %d", who, h[1], kSpgemmMaxW);
+        return set_error(MPBP_ERR_OVERFLOW, "%s: %d rows have an %s row wider than %d", who, h[1],
+                         wide ? "inner" : "output or inner", kSpgemmMaxW);
     if (h[0] & kRefillMissing)
         return set_error(MPBP_ERR_PATTERN, "%s: %d rows of C lack a column their product holds", who, h[1]);
     return MPBP_OK;
 }
 }  // namespace
 
-int mpbp_spgemm_refill(const mpbp_csr* A, const mpbp_csr* B, double alpha, const mpbp_csr* C, void* stream) {
+static int spgemm_refill(const char* who, bool wide, const mpbp_csr* A, const mpbp_csr* B, double alpha,
+                         const mpbp_csr* C, void* stream) {
     int rc = check_csr(A);
     if (!rc) rc = check_csr(B);
     if (!rc) rc = check_csr(C);
     if (rc) return rc;
     if (A->ncols != B->nrows || C->nrows != A->nrows || C->ncols != B->ncols)
-        return set_error(MPBP_ERR_ARG, "spgemm_refill: shape mismatch");
-    return run_refill("spgemm_refill", kRefillPair, A, B, nullptr, 1.0, alpha, C, stream);
+        return set_error(MPBP_ERR_ARG, "%s: shape mismatch", who);
+    return run_refill(who, kRefillPair, A, B, nullptr, 1.0, alpha, C, stream, wide);
+}
+int mpbp_spgemm_refill(const mpbp_csr* A, const mpbp_csr* B, double alpha, const mpbp_csr* C, void* stream) {
+    return spgemm_refill("spgemm_refill", false, A, B, alpha, C, stream);
+}
+int mpbp_spgemm_refill_wide(const mpbp_csr* A, const mpbp_csr* B, double alpha, const mpbp_csr* C, void* stream) {
+    return spgemm_refill("spgemm_refill_wide", true, A, B, alpha, C, stream);
 }
 
-int mpbp_triple_refill(const mpbp_csr* X, const mpbp_csr* Y, const mpbp_csr* Z, int32_t assoc, double alpha_inner,
-                       double alpha_outer, const mpbp_csr* C, void* stream) {
+static int triple_refill(const char* who, bool wide, const mpbp_csr* X, const mpbp_csr* Y, const mpbp_csr* Z,
+                         int32_t assoc, double alpha_inner, double alpha_outer, const mpbp_csr* C, void* stream) {
     int rc = check_csr(X);
     if (!rc) rc = check_csr(Y);
     if (!rc) rc = check_csr(Z);
     if (!rc) rc = check_csr(C);
     if (rc) return rc;
     if (assoc != MPBP_ASSOC_LEFT && assoc != MPBP_ASSOC_RIGHT)
-        return set_error(MPBP_ERR_ARG, "triple_refill: assoc must be MPBP_ASSOC_LEFT or MPBP_ASSOC_RIGHT");
+        return set_error(MPBP_ERR_ARG, "%s: assoc must be MPBP_ASSOC_LEFT or MPBP_ASSOC_RIGHT", who);
     if (X->ncols != Y->nrows || Y->ncols != Z->nrows || C->nrows != X->nrows || C->ncols != Z->ncols)
-        return set_error(MPBP_ERR_ARG, "triple_refill: shape mismatch");
-    return run_refill("triple_refill", assoc == MPBP_ASSOC_LEFT ? kRefillLeft : kRefillRight, X, Y, Z, alpha_inner,
-                      alpha_outer, C, stream);
+        return set_error(MPBP_ERR_ARG, "%s: shape mismatch", who);
+    return run_refill(who, assoc == MPBP_ASSOC_LEFT ? kRefillLeft : kRefillRight, X, Y, Z, alpha_inner, alpha_outer, C,
+                      stream, wide);
+}
+int mpbp_triple_refill(const mpbp_csr* X, const mpbp_csr* Y, const mpbp_csr* Z, int32_t assoc, double alpha_inner,
+                       double alpha_outer, const mpbp_csr* C, void* stream) {
+    return triple_refill("triple_refill", false, X, Y, Z, assoc, alpha_inner, alpha_outer, C, stream);
+}
+int mpbp_triple_refill_wide(const mpbp_csr* X, const mpbp_csr* Y, const mpbp_csr* Z, int32_t assoc, double alpha_inner,
+                            double alpha_outer, const mpbp_csr* C, void* stream) {
+    return triple_refill("triple_refill_wide", true, X, Y, Z, assoc, alpha_inner, alpha_outer, C, stream);
 }
 
 int64_t mpbp_plan_row_blocks(const int32_t* row_ptr, int32_t row_begin, int32_t row_end,
@@ -6143,4 +6365,6 @@ int mpbp_event_elapsed_ms(void* start, void* stop, float* ms) {
 // and bench.py's apply -- byte-identical kernels -- measured 0.9-1.0 % slower in alternating runs (6980-7006 against
 // 7059-7068 applies/s); these 0xF00 read-only bytes put .text back at 0x800 (7045-7078).  DESIGN.md section 4f.
 // Re-derive or drop it when the kernel set changes (llvm-objdump -h on the unbundled gfx950 code object).
-extern "C" __device__ __attribute__((used)) const char mpbp_text_pad[0xF00] = {1};
+// Re-derived with the any-size transfer and wide product kernels: their descriptors and metadata moved .text by
+// 0x3900 (to page offset 0x100 under the 0xF00 pad); 0x600 puts it back at 0x800.
+extern "C" __device__ __attribute__((used)) const char mpbp_text_pad[0x600] = {1};

@@ -720,6 +720,9 @@ class PartitionedMultigrid:
     def __init__(self, g, part: RowPartition, nfields: int, group=None, min_cells: int = 1 << 14,
                  max_part_levels: int | None = None):
         # g: a LocalHierarchy (this rank's rows only) or a whole mg.Multigrid (every rank holds it)
+        if getattr(g, "coarsen", "even") != "even":
+            raise ValueError(f"coarsen={g.coarsen!r} is not available under the row partition: the rows' halving and "
+                             'ghost depths assume 2:1 transfers; use coarsen="even" here')
         g = g if isinstance(g, LocalHierarchy) else _GlobalLevels(g)
         self.g, self.part0, self.nf, self.group = g, part, nfields, group
         dev = g.device
@@ -1140,6 +1143,9 @@ class DistributedSchurPreconditioner(PlanProfiling):
             if getattr(inner, "accel", None) is not None:
                 raise ValueError(f"{name}: Chebyshev-accelerated multigrid (accel={inner.accel!r}) is not available on "
                                  "the row-partitioned hierarchies; use accel=None here")
+            if getattr(inner, "coarsen", "even") != "even":
+                raise ValueError(f"{name}: coarsen={inner.coarsen!r} is not available under the row partition; use "
+                                 'coarsen="even" here')
         import torch.distributed as dist
         from .preconditioner import MultiphaseBlockPreconditioner
         from .solve import InnerSolver, _check_numerics

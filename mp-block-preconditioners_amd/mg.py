@@ -5,7 +5,7 @@ its own comments: "In IBAMR, we'd use Multigrid PC with Jacobi smoother" (solve.
 that choice on the GPU:
 
 * levels: the periodic n x n MAC grid coarsened by 2 per direction down to n <= ``coarsest`` (at least once;
-  odd n stops);
+  odd n stops -- or, with ``coarsen="any"``, coarsens to n // 2 by interpolated transfers, so any n >= 5 works);
 * transfers: per field, linear interpolation along each axis -- cell-centred (p; u along y; v along x)
   or node-centred (u along x, v along y) -- as CSR P, and R = P^T (``mpbp_mg_transfer_*``, exact values);
 * coarse operators: Galerkin A_{l+1} = R (A_l P) with the library's SpGEMM (every product kept);
@@ -38,18 +38,29 @@ FIELDS_VELOCITY = ((CELL, NODE), (NODE, CELL), (CELL, NODE), (NODE, CELL))
 FIELDS_PRESSURE = ((CELL, CELL),)
 
 
-def transfer(n: int, fields, which: int, device) -> DeviceCSR:
-    """P (which = MG_P: fine x coarse) or R = P^T (MG_R) of the n x n grid, built on the GPU."""
+COARSENINGS = ("even", "any")
+
+
+def _check_coarsen(coarsen: str):
+    if coarsen not in COARSENINGS:
+        raise ValueError(f"coarsen must be one of {COARSENINGS}, not {coarsen!r}")
+
+
+def transfer(n: int, fields, which: int, device, coarsen: str = "even") -> DeviceCSR:
+    """P (which = MG_P: fine x coarse) or R = P^T (MG_R) of the n x n grid, built on the GPU.  coarsen="even": n even,
+    the 2:1 lists; "any": n >= 5 of either parity coarsened to n // 2, each fine point interpolated linearly from its
+    two coarse neighbours (mpbp_mg_transfer_any_*; for even n the same matrix bit for bit)."""
+    _check_coarsen(coarsen)
+    count, fill = ((lib().mpbp_mg_transfer_any_count, lib().mpbp_mg_transfer_any_fill) if coarsen == "any" else
+                   (lib().mpbp_mg_transfer_count, lib().mpbp_mg_transfer_fill))
     kinds = np.ascontiguousarray(np.asarray(fields, dtype=np.int32).reshape(-1))
     nf = len(fields)
     rows = nf * (n * n if which == _lib.MG_P else (n // 2) ** 2)
     cols = nf * ((n // 2) ** 2 if which == _lib.MG_P else n * n)
-    row_nnz = torch.empty(rows, dtype=torch.int32, device=device)
-    check(lib().mpbp_mg_transfer_count(n, nf, kinds.ctypes.data_as(ctypes.c_void_p), which, ptr(row_nnz),
-                                       stream_handle()))
+    row_nnz = torch.empty(max(rows, 1), dtype=torch.int32, device=device)[:rows]
+    check(count(n, nf, kinds.ctypes.data_as(ctypes.c_void_p), which, ptr(row_nnz), stream_handle()))
     rp, ci, va = csr_from_row_nnz(row_nnz, (rows, cols), device)
-    check(lib().mpbp_mg_transfer_fill(n, nf, kinds.ctypes.data_as(ctypes.c_void_p), which, ptr(rp), ptr(ci),
-                                      ptr(va), stream_handle()))
+    check(fill(n, nf, kinds.ctypes.data_as(ctypes.c_void_p), which, ptr(rp), ptr(ci), ptr(va), stream_handle()))
     return DeviceCSR(rp, ci, va, (rows, cols))
 
 
@@ -233,11 +244,20 @@ def dense_inverse_csr(A: DeviceCSR) -> tuple[DeviceCSR, np.ndarray]:
     return M, inv
 
 
-def level_sizes(n: int, coarsest: int) -> list[int]:
-    """Grid sizes of the hierarchy: halve while even, down to <= coarsest (at least one coarsening)."""
+def _stop_coarsening(m: int, coarsest: int, nlevels: int, coarsen: str) -> bool:
+    """Whether size m is the hierarchy's last level when nlevels levels exist (at least one coarsening)."""
+    if m <= coarsest and nlevels > 1:
+        return True
+    return m < 5 if coarsen == "any" else bool(m % 2 or m // 2 < 2)
+
+
+def level_sizes(n: int, coarsest: int, coarsen: str = "even") -> list[int]:
+    """Grid sizes of the hierarchy, down to <= coarsest (at least one coarsening).  coarsen="even": halve while even;
+    "any": halve with floor whatever the parity (an odd level's transfers interpolate, transfer(coarsen="any"))."""
+    _check_coarsen(coarsen)
     sizes = [n]
     m = n
-    while not (m % 2 or (m <= coarsest and len(sizes) > 1) or m // 2 < 2):
+    while not _stop_coarsening(m, coarsest, len(sizes), coarsen):
         m //= 2
         sizes.append(m)
     return sizes
@@ -260,6 +280,11 @@ class Multigrid:
              over the same ``cycles`` V-cycles for spec(M A) in [1 - rho, 1] (mpbp_mg_accel_coeffs, mpbp_mg_combine) --
              no inner products, no extra operator apply, still a linear operator.  Needs a symmetric cycle (pre ==
              post) and a nonsingular operator.
+    coarsen  "even" (default): halve while the size is even, the first odd size is the coarsest level.  "any": halve with
+             floor whatever the parity (n >= 5), an odd level's P / R interpolating each fine point from its two coarse
+             neighbours (transfer(coarsen="any")); Galerkin rows below an odd level reach 86 entries, so the products
+             and refresh take the wide forms (<= 128).  Odd-derived levels get no stencil-values copy and no fused
+             residual-restriction kernel (their rows are ragged); everything else, accel included, is unchanged.
     rho      the contraction bound of one V-cycle; None: estimated here (and again by refresh) as ACCEL_RHO_MARGIN x
              the largest of contraction()'s last three ratios -- setup work that synchronises with the host
     """
@@ -267,8 +292,9 @@ class Multigrid:
     def __init__(self, A: DeviceCSR, n: int, fields=FIELDS_PRESSURE, pre: int = 2, post: int = 2, cycles: int = 1,
                  ratio: float = 4.0, coarsest: int = 8, diag: torch.Tensor | None = None, sell: bool = True,
                  fine_sell: bool = True, svl_min_rows: int | None | str = "default", kernel_opts: dict | None = None,
-                 accel: str | None = None, rho: float | None = None):
+                 accel: str | None = None, rho: float | None = None, coarsen: str = "even"):
         nf = len(fields)
+        _check_coarsen(coarsen)
         if accel not in ACCELS:
             raise ValueError(f"accel must be one of {ACCELS}, not {accel!r}")
         if accel is not None and pre != post:
@@ -278,18 +304,24 @@ class Multigrid:
             raise ValueError("rho needs accel and 0 < rho < 1")
         if A.shape != (nf * n * n, nf * n * n):
             raise ValueError(f"operator {A.shape} is not {nf} fields of a {n} x {n} grid")
-        if n < 4 or n % 2 or n // 2 < 2:
+        if coarsen == "any":
+            if n < 5:
+                raise ValueError('multigrid with coarsen="any" needs a grid n >= 5')
+        elif n < 4 or n % 2 or n // 2 < 2:
             raise ValueError("multigrid needs an even grid n >= 4")
         if pre < 1 or post < 1 or cycles < 1:
             raise ValueError("pre, post and cycles must be >= 1")
         self.n, self.fields, self.pre, self.post, self.cycles, self.ratio = n, tuple(fields), pre, post, cycles, ratio
-        self.coarsest = coarsest
+        self.coarsest, self.coarsen = coarsest, coarsen
         dev = A.device
         self.device = dev
-        sizes = level_sizes(n, coarsest)
+        sizes = level_sizes(n, coarsest, coarsen)
         if nf * sizes[-1] ** 2 > MAX_COARSE_ROWS:   # refuse before any Galerkin product is formed
-            raise ValueError(f"grid {n} coarsens to {sizes} (stopping at an odd size): the coarsest level's "
-                             f"{nf * sizes[-1] ** 2} rows exceed the dense inverse's {MAX_COARSE_ROWS}")
+            why, hint = (("stopping at `coarsest`", f": lower `coarsest` (now {coarsest})") if coarsen == "any" else
+                         ("stopping at an odd size", '; coarsen="any" coarsens odd sizes too'))
+            raise ValueError(f"grid {n} coarsens to {sizes} ({why}): the coarsest level's "
+                             f"{nf * sizes[-1] ** 2} rows exceed the dense inverse's {MAX_COARSE_ROWS}{hint}")
+        wide = coarsen == "any"   # Galerkin rows below an odd level reach 86 entries
         self.ops, self.diags, self.R, self.P, self.bounds, self.sizes = [], [], [], [], [], []
         m = n
         while True:
@@ -299,13 +331,14 @@ class Multigrid:
             self.diags.append(d)
             self.bounds.append((lmax / ratio, lmax))
             self.sizes.append(m)
-            if m % 2 or (m <= coarsest and len(self.ops) > 1) or m // 2 < 2:   # (at least one coarsening)
+            if _stop_coarsening(m, coarsest, len(self.ops), coarsen):   # (at least one coarsening)
                 break
-            P = transfer(m, fields, _lib.MG_P, dev)
-            R = transfer(m, fields, _lib.MG_R, dev)
+            rule = "any" if m % 2 else "even"   # (an even level's lists are the same under either rule)
+            P = transfer(m, fields, _lib.MG_P, dev, coarsen=rule)
+            R = transfer(m, fields, _lib.MG_R, dev, coarsen=rule)
             self.P.append(P)
             self.R.append(R)
-            A = spgemm(R, spgemm(A, P))
+            A = spgemm(R, spgemm(A, P, wide=wide), wide=wide)
             m //= 2
         if len(self.ops) < 2:
             raise ValueError(f"grid {n} gives a single level (coarsest={coarsest})")
@@ -406,20 +439,20 @@ class Multigrid:
     def refresh(self, diag: torch.Tensor | None = None, timings: dict | None = None):
         """New values on the same grid: level 0's operator (the caller's) already holds them.  Recomputes, in place at
         every address the hierarchy's struct holds, each coarser operator (one fused R (A P) launch per level,
-        mpbp_triple_refill, no A P intermediate), every level's diagonal and smoothing interval, the SELL and
-        stencil-values copies and the coarsest pseudo-inverse -- what a fresh Multigrid over the same operator computes,
+        mpbp_triple_refill -- its wide form under coarsen="any" --, no A P intermediate), every level's diagonal and
+        smoothing interval, the SELL and stencil-values copies and the coarsest pseudo-inverse -- what a fresh Multigrid over the same operator computes,
         bit for bit, with no structural work.  diag: level 0's new diagonal (default: recomputed; the tensor given to
         the constructor, refreshed by the caller, may be passed again).  timings: seconds per phase, each synchronised.
         An estimated acceleration rho is estimated again (phase "accel_rho"; an explicit one stays).
         Graphs captured before carry the old smoothing intervals (and the acceleration's coefficients) as kernel
         arguments: capture again."""
+        triple_refill = lib().mpbp_triple_refill_wide if self.coarsen == "any" else lib().mpbp_triple_refill
         for l, A in enumerate(self.ops):
             if l > 0:
                 with timed_phase(timings, "galerkin"):
-                    check(lib().mpbp_triple_refill(ctypes.byref(self.R[l - 1].cstruct()),
-                                                   ctypes.byref(self.ops[l - 1].cstruct()),
-                                                   ctypes.byref(self.P[l - 1].cstruct()), _lib.ASSOC_RIGHT, 1.0, 1.0,
-                                                   ctypes.byref(A.cstruct()), stream_handle()))
+                    check(triple_refill(ctypes.byref(self.R[l - 1].cstruct()), ctypes.byref(self.ops[l - 1].cstruct()),
+                                        ctypes.byref(self.P[l - 1].cstruct()), _lib.ASSOC_RIGHT, 1.0, 1.0,
+                                        ctypes.byref(A.cstruct()), stream_handle()))
             with timed_phase(timings, "diag_bounds"):
                 d = self.diags[l]
                 if l == 0 and diag is not None:
@@ -471,5 +504,5 @@ class Multigrid:
 
     def __repr__(self):
         return (f"Multigrid(levels={self.sizes}, fields={len(self.fields)}, pre={self.pre}, post={self.post}, "
-                f"cycles={self.cycles}, ratio={self.ratio}"
+                f"cycles={self.cycles}, ratio={self.ratio}" + (", coarsen='any'" if self.coarsen == "any" else "")
                 + (f", accel={self.accel!r}, rho={self._rho:.4g}" if self.accel else "") + ")")

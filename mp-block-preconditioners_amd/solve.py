@@ -38,6 +38,8 @@ class InnerSolver:
     lmin   lower end of the Chebyshev interval; None -> lmax / ratio
     pre, post, smooth_ratio, coarsest   "mg" only: smoothing sweeps per level, smoothing interval
            [lmax / smooth_ratio, lmax], coarsening stops at n <= coarsest
+    coarsen  "mg" only: "even" halves while the grid size is even (n = m 2^k with a small odd m); "any" coarsens odd
+           sizes too, by interpolated transfers, so any n >= 5 works (mg.Multigrid; one GPU only)
     accel, rho   "mg" only: accel="chebyshev" runs the `sweeps` V-cycles as a fixed Chebyshev semi-iteration (about 40x
            per cycle instead of 12x for F; needs pre == post and a nonsingular operator, so F, not Gt_G); rho is one
            cycle's contraction bound, None -> estimated at construction and on every refresh (mg.Multigrid)
@@ -53,6 +55,7 @@ class InnerSolver:
     coarsest: int = 16     # dense coarsest inverse at 16^2: 1024 x 1024 for F (one fewer latency-bound level than 8^2)
     accel: str | None = None
     rho: float | None = None
+    coarsen: str = "even"
 
     def __post_init__(self):
         self._check_accel()
@@ -76,7 +79,7 @@ class InnerSolver:
         if self.kind == "mg":
             return InnerSolver("mg", int(self.sweeps), 0.0, 0.0, self.ratio, int(self.pre), int(self.post),
                                float(self.smooth_ratio), int(self.coarsest), self.accel,
-                               None if self.rho is None else float(self.rho))
+                               None if self.rho is None else float(self.rho), self.coarsen)
         if self.kind != "chebyshev":
             raise ValueError(f"unknown inner solver {self.kind!r}")
         lmax = float(self.lmax) if self.lmax is not None else M.gershgorin(diag)
@@ -87,7 +90,7 @@ class InnerSolver:
         from .mg import Multigrid
         return Multigrid(M, n, fields, pre=self.pre, post=self.post, cycles=int(self.sweeps),
                          ratio=self.smooth_ratio, coarsest=self.coarsest, diag=diag, fine_sell=False,
-                         accel=self.accel, rho=self.rho)
+                         accel=self.accel, rho=self.rho, coarsen=self.coarsen)
 
     def cstruct(self):
         kind = {"chebyshev": _lib.INNER_CHEBYSHEV, "jacobi": _lib.INNER_JACOBI, "mg": _lib.INNER_MG}[self.kind]

@@ -1,6 +1,6 @@
 // C ABI, part 3: the multigrid entries (mg_fields, transfers, mpbp_mg_solve, acceleration coefficients) and
-// mpbp_stokes_apply_part.  Needs mpbp.hip's kernels (MgFields, k_mg_transfer, launch_stokes_a), abi_stencil.inc,
-// schur_ops.inc, mg_solve.inc and mg_accel.inc.
+// mpbp_stokes_apply_part.  Needs mpbp.hip's MgFields and k_mg_transfer, launch_stokes_a (pg_stencil.inc),
+// abi_stencil.inc, schur_ops.inc, mg_solve.inc and mg_accel.inc.
 // A fragment of mpbp.hip, included there once and in order: not a self-contained header.
 
 // ======================================================= multigrid (C ABI) ====

@@ -1,6 +1,7 @@
-// C ABI, part 2 (part 1 is the "C ABI" section of mpbp.hip itself): SELL, the F stencil (make_fstencil), the
-// pressure stencils (make_pgstencil) and mpbp_stokes_apply.  Needs mpbp.hip's kernel sections: the epilogues,
-// FStencilDev, launch_march, with_f_policy, PGDev and the D / G / Gt_G policies, launch_stokes_a, launch_sell.
+// C ABI, part 2 (part 1 is abi_core.inc): SELL, the F stencil (make_fstencil), the
+// pressure stencils (make_pgstencil) and mpbp_stokes_apply.  Needs mpbp.hip's epilogues and FStencilDev, launch_march
+// and with_f_policy (f_solve_w.inc), PGDev, the D / G / Gt_G policies and launch_stokes_a (pg_stencil.inc) and
+// launch_sell (launchers.inc).
 // A fragment of mpbp.hip, included there once and in order: not a self-contained header.
 
 // ============================================================== SELL ABI ====

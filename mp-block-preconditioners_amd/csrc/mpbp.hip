@@ -5,12 +5,13 @@
 // sequential checker oracle/csr_oracle.c in the same order (row sums left to
 // right from 0.0, no fused multiply-add), so results are bit-identical to it.
 //
-// This file is the one translation unit.  It holds the device kernels, their launchers and the first section of the
-// C ABI; the rest of the C ABI and the host-side algorithms live in the csrc/*.inc fragments included at its end, in
-// this order (map: DESIGN.md section 4).
+// This file is the one translation unit.  It holds the prelude and the device kernels up to the marching kernels; the
+// tiled F, pressure-side and fused multigrid kernels, the launchers, the C ABI and the host-side algorithms live
+// in the csrc/*.inc fragments included at its end, in this order (map: DESIGN.md section 4).
 #include <hip/hip_runtime.h>
 
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -23,16 +24,72 @@
 namespace {
 
 thread_local char g_err[1024] = "";
+int set_error(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
 // Kernel choices (mpbp_kernel_opts, include/mpbp.h): the process defaults (mpbp_set_*), and the choices of the plan
 // being applied -- mpbp_schur_apply / mpbp_mg_solve install their plan's copy for the duration of the call (OptsScope),
 // so two preconditioners with different choices coexist and a captured graph holds its own plan's choices.
+// kOpts is the one table of them: line i is the struct's word i (the static_assert below), with the default and the
+// lowest and highest value a setter or a plan may hold.  g_defaults, check_opts and the mpbp_set_* entry points
+// (set_default) read it.  gtg_tpb alone is no interval: 256 or 512, its two ends (check_opts says so).
 // Measured defaults: march_rows 0 = the count that fills one round of workgroups (256^2 1 row -> 13.5k applies/s vs
 // 7.6k at 4; 1024^2 4; 2048^2 16 -> 753 vs 727).
-mpbp_kernel_opts g_defaults = {
-    /*march_rows*/ 0, /*init_diag*/ 1, /*f_pair*/ 1, /*f_direct*/ 0, /*gtg_fused*/ 1, /*gtg_tpb*/ 512, /*gtg_drhs*/ 1,
-    /*q13_sym*/ 1, /*f_tile*/ 1, /*f_solve*/ 1, /*mg_galerkin_mf*/ 2, /*mg_galerkin_mf_p*/ 1, /*pg_direct*/ 1,
-    /*mg_group_rows*/ 65536, /*mg_svl*/ 1, /*mg_mf_transfer*/ 1, /*csr_table*/ 1, /*mg_fuse_l0*/ 1,
-    /*mg_coarse_tree*/ 0, /*f_solve_tile*/ 1, /*q13_mf*/ 0, /*mg_fuse_small*/ 1, /*gtg_solve_tile*/ 1, {0}};
+struct KOpt {
+    size_t offset;
+    const char* name;
+    int32_t def, lo, hi;
+};
+#define MPBP_KOPT(f, def, lo, hi) {offsetof(mpbp_kernel_opts, f), #f, def, lo, hi}
+constexpr KOpt kOpts[] = {
+    MPBP_KOPT(march_rows, 0, 0, 4096),
+    MPBP_KOPT(init_diag, 1, 0, 1),
+    MPBP_KOPT(f_pair, 1, 0, 1),
+    MPBP_KOPT(f_direct, 0, 0, 1),
+    MPBP_KOPT(gtg_fused, 1, 0, 1),
+    MPBP_KOPT(gtg_tpb, 512, 256, 512),
+    MPBP_KOPT(gtg_drhs, 1, 0, 1),
+    MPBP_KOPT(q13_sym, 1, 0, 1),
+    MPBP_KOPT(f_tile, 1, 0, 1),
+    MPBP_KOPT(f_solve, 1, 0, 1),
+    MPBP_KOPT(mg_galerkin_mf, 2, 0, 2),
+    MPBP_KOPT(mg_galerkin_mf_p, 1, 0, 1),
+    MPBP_KOPT(pg_direct, 1, 0, 1),
+    MPBP_KOPT(mg_group_rows, 65536, 0, INT32_MAX),
+    MPBP_KOPT(mg_svl, 1, 0, 1),
+    MPBP_KOPT(mg_mf_transfer, 1, 0, 1),
+    MPBP_KOPT(csr_table, 1, 0, 1),
+    MPBP_KOPT(mg_fuse_l0, 1, 0, 1),
+    MPBP_KOPT(mg_coarse_tree, 0, 0, 1),
+    MPBP_KOPT(f_solve_tile, 1, 0, 1),
+    MPBP_KOPT(q13_mf, 0, 0, 1),
+    MPBP_KOPT(mg_fuse_small, 1, 0, 1),
+    MPBP_KOPT(gtg_solve_tile, 1, 0, 1),
+};
+#undef MPBP_KOPT
+constexpr size_t kNumOpts = sizeof(kOpts) / sizeof(kOpts[0]);
+constexpr bool opts_cover_struct() {   // nothing skipped, doubled or out of order
+    for (size_t i = 0; i < kNumOpts; ++i)
+        if (kOpts[i].offset != i * sizeof(int32_t)) return false;
+    return true;
+}
+static_assert(kNumOpts == (sizeof(mpbp_kernel_opts) - sizeof(mpbp_kernel_opts::reserved)) / sizeof(int32_t) &&
+                  opts_cover_struct(),
+              "kOpts needs one line per field of mpbp_kernel_opts, in struct order");
+// the struct as its int32 words (it holds nothing else: the static_assert above)
+inline int32_t* opt_words(mpbp_kernel_opts& o) { return reinterpret_cast<int32_t*>(&o); }
+inline const int32_t* opt_words(const mpbp_kernel_opts& o) { return reinterpret_cast<const int32_t*>(&o); }
+inline mpbp_kernel_opts default_opts() {
+    mpbp_kernel_opts o{};
+    for (size_t i = 0; i < kNumOpts; ++i) opt_words(o)[i] = kOpts[i].def;
+    return o;
+}
+mpbp_kernel_opts g_defaults = default_opts();
 thread_local const mpbp_kernel_opts* t_opts = nullptr;
 inline const mpbp_kernel_opts& KO() { return t_opts ? *t_opts : g_defaults; }
 struct OptsScope {   // installs a plan's kernel choices (when it has its own) for one entry-point call
@@ -44,27 +101,19 @@ struct OptsScope {   // installs a plan's kernel choices (when it has its own) f
 };
 inline int pg_rows() { return KO().march_rows; }   // rows per workgroup of the D / G / Gt_G marching kernels: as F
 // a plan's kernel choices must be values the setters accept
-int set_error(int code, const char* fmt, ...);
 inline int check_opts(const mpbp_kernel_opts* o, const char* who) {
     if (!o) return MPBP_OK;
-    const bool ok = o->march_rows >= 0 && o->march_rows <= 4096 && (o->gtg_tpb == 256 || o->gtg_tpb == 512) &&
-                    o->f_solve_tile >= 0 && o->f_solve_tile <= 1 &&
-                    o->mg_galerkin_mf >= 0 && o->mg_galerkin_mf <= 2 && o->mg_group_rows >= 0 &&
-                    (o->init_diag | o->f_pair | o->f_direct | o->gtg_fused | o->gtg_drhs | o->q13_sym | o->f_tile |
-                     o->f_solve | o->mg_galerkin_mf_p | o->pg_direct | o->mg_svl | o->mg_mf_transfer | o->csr_table |
-                     o->mg_fuse_l0 | o->mg_coarse_tree | o->q13_mf | o->mg_fuse_small | o->gtg_solve_tile) >= 0 &&
-                    (o->init_diag | o->f_pair | o->f_direct | o->gtg_fused | o->gtg_drhs | o->q13_sym | o->f_tile |
-                     o->f_solve | o->mg_galerkin_mf_p | o->pg_direct | o->mg_svl | o->mg_mf_transfer | o->csr_table |
-                     o->mg_fuse_l0 | o->mg_coarse_tree | o->q13_mf | o->mg_fuse_small | o->gtg_solve_tile) <= 1;
+    bool ok = o->gtg_tpb == 256 || o->gtg_tpb == 512;
+    for (size_t i = 0; i < kNumOpts; ++i)
+        ok = ok && opt_words(*o)[i] >= kOpts[i].lo && opt_words(*o)[i] <= kOpts[i].hi;
     return ok ? MPBP_OK : set_error(MPBP_ERR_ARG, "%s: kernel options out of range", who);
 }
-
-int set_error(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
+// the body of every mpbp_set_*: the process default of the field at `offset`, refused outside its line's range
+inline int set_default(size_t offset, int32_t v) {
+    const KOpt& k = kOpts[offset / sizeof(int32_t)];
+    if (v < k.lo || v > k.hi) return set_error(MPBP_ERR_ARG, "%s must be in [%d, %d]", k.name, k.lo, k.hi);
+    opt_words(g_defaults)[offset / sizeof(int32_t)] = v;
+    return MPBP_OK;
 }
 
 #define MPBP_HIP(call)                                                                      \
@@ -3233,3123 +3282,15 @@ int launch_march_fixed(const S& P, const XS& xs, Epi epi, int rows_per_block, hi
     return MPBP_OK;
 }
 
-// ---- two F sweeps per launch on a 2D tile, tolerance mode (k_ftile) ----
-// A workgroup owns a 64 x 8 tile of cells (two per lane: rows t>>6 and 4 + t>>6 of the tile, column t & 63).  It first
-// stages, with coalesced loads, thn and (!INIT) x_in over the tile plus a two-cell halo (68 x 12 cells, 32.6 KB of LDS):
-// every stencil operand after that is an LDS read at a constant offset from the cell's slot, with no periodic wrap and
-// no 64-bit address arithmetic per neighbour.  Level A runs on the tile plus a one-cell halo (66 x 10 cells): INIT, the
-// pointwise first iterate x0 = d0 = c2_0 b / diag (diag rebuilt from thn, FStencilFast::rdiag4); otherwise sweep s from
-// x_in and d_in.  Level A's x replaces x_in in the same LDS slots (after a barrier: its stencil reads x_in around the
-// cell), its d and the reciprocal diagonals of the lane's two tile cells stay in registers; level B (sweep 1, or s + 1)
-// computes the tile from LDS, reusing those diagonals, and writes x_out (and d_out when SD).  Every workgroup is
-// independent.  Each level performs the IEEE operations of the marching kernels' tolerance-mode rows and updates, so
-// k_ftile is bit-identical to k_march_init + (k_march or) k_march2.  One GPU, whole grid.
-// The LDS-tiled stencil kernels read each operand with its own ds_read_b64 (2 LDS cycles per wave on gfx950) instead
-// of letting the compiler pair neighbouring slots into ds_read2_b64 (8 cycles: half the bytes per clock).
-#ifndef MPBP_LDS_SINGLE
-#define MPBP_LDS_SINGLE 1
-#endif
-#if MPBP_LDS_SINGLE && defined(__HIP_DEVICE_COMPILE__)   // (a device-code attribute: the host pass has no such feature)
-#define MPBP_LDS_READS __attribute__((target("no-load-store-opt")))
-#else
-#define MPBP_LDS_READS
-#endif
-constexpr int kFTW = 64, kFTH = 8, kFSW = kFTW + 4, kFSH = kFTH + 4, kFSN = kFSW * kFSH;
-template <int W, int H>
-struct XTileT {  // 4 fields over a W x H block of LDS ([4][H][W]), slot (0, 0) = virtual grid cell (rb, cb)
-    const double* x;
-    int rb, cb;
-    __device__ double X(int f, int r, int c) const { return x[(f * H + (r - rb)) * W + (c - cb)]; }
-};
-constexpr int kFAW = kFTW + 2, kFAH = kFTH + 2, kFAN = kFAW * kFAH;   // level A's cells: the tile + 1 halo
-template <int W>
-struct TTileT {  // staged thn at virtual grid coordinates, W columns per staged row
-    const double* t;
-    int rb, cb;
-    __device__ double T(int sph, int r, int c) const {
-        const double v = t[(r - rb) * W + (c - cb)];
-        return sph ? 1.0 - v : v;
-    }
-};
-template <int W>
-struct TTileWT {  // staged thn at wrapped grid coordinates (GxBT::b: its wrap tests need the wrapped row / column)
-    const double* t;
-    int rb, cb, n;
-    __device__ double T(int sph, int r, int c) const {
-        int lr = r - rb, lc = c - cb;
-        lr = lr < 0 ? lr + n : (lr >= n ? lr - n : lr);
-        lc = lc < 0 ? lc + n : (lc >= n ? lc - n : lc);
-        const double v = t[lr * W + lc];
-        return sph ? 1.0 - v : v;
-    }
-};
-struct FTile {
-    const double* x_in;   // !INIT: x_{s-1}
-    const double* d_in;   // !INIT: d_{s-1}
-    const double* b;      // BNone: the right-hand side
-    const double* sub;    // SUB: level B returns sub - x
-    double* x_out;
-    double* d_out;        // SD
-    double c1a, c2a, c1b, c2b;   // INIT: c2a = c2_0 (c1a unused)
-    int dzero = 0;        // !INIT: d_{s-1} is +0.0 (a restart: multigrid post-smoothing), d_in is not read
-    const double* xc = nullptr;   // !INIT: x_in + P_0 xc (the coarse correction of a multigrid level 0, the F
-                                  // hierarchy's MAC kinds) is the iterate -- the prolongation launch folded in
-};
-
-// multigrid level 1's tile and windows (k_gal1; the level-0 fused kernels stage the same windows)
-constexpr int kG1W = 32, kG1H = 4;                          // coarse tile
-constexpr int kG1FW = 2 * kG1W + 2, kG1FH = 2 * kG1H + 2;   // t1: fine [2 c0 - 1, 2 c0 + 2 W + 1)
-constexpr int kG1PW = kG1FW + 2, kG1PH = kG1FH + 2;         // t0 and thn: one more fine cell each side
-constexpr int kG1CW = kG1W + 4;                             // coarse x: [c0 - 2, c0 + W + 2)
-template <int KY, int KX, int S = kG1CW>
-__device__ inline double g1_p(const double* xf, int gr, int gc, int nc, int rb, int cb);
-template <int KY, int KX, int S = kG1CW>
-__device__ inline double g1_p_in(const double* xf, int r, int c);
-template <int KY, int KX, int W, int OFF>
-__device__ inline double g1_rw_in(const double* tf, int lr, int lc);
-__device__ inline bool g1_inner(int cr0, int cc0, int th, int tw, int nc);
-template <bool INIT, bool SUB, bool SD, class BS, bool PRO = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) MPBP_LDS_READS k_ftile(FStencilFast P, FTile a, BS bs) {
-    __shared__ double xs[INIT ? 1 : 4 * kFSN];   // !INIT: x_in over the tile + 2 halo
-    __shared__ double ts[kFSN];                   // thn over the tile + 2 halo
-    __shared__ double xl[4 * kFAN];               // level A's x over the tile + 1 halo (PRO: first the coarse window)
-    const int n = P.n;
-    const int tx = (n + kFTW - 1) / kFTW;
-    const int bk = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int r0 = (bk / tx) * kFTH, c0 = (bk % tx) * kFTW;
-    const int rb = r0 - 2, cb = c0 - 2;
-    const int tid = threadIdx.x;
-    const int nn = n * n;
-    // PRO: the coarse correction over [r0 / 2 - 2, r0 / 2 + 6) x [c0 / 2 - 2, c0 / 2 + 34) of 4 fields (k_gal1's window)
-    constexpr int CW = kFTW / 2 + 4, CH = kFTH / 2 + 4, CN = CW * CH;
-    static_assert(!PRO || 4 * CN <= 4 * kFAN, "the coarse window fits the level-A buffer");
-    static_assert(CW == kG1CW && kFSW == kG1PW && kFSH == kG1PH, "g1_p_in's window geometry");
-    const int nc = n >> 1, ncc = nc * nc, cr0 = r0 >> 1, cc0 = c0 >> 1;
-    // stage thn (and x_in) over rows r0-2 .. r0+9, columns c0-2 .. c0+65: every load issued before the first LDS store
-    {
-        constexpr int IT = (kFSN + 255) / 256, NF = INIT ? 1 : 5, IC = PRO ? (4 * CN + 255) / 256 : 1;
-        double v[IT][NF], vc[IC];
-        if constexpr (PRO) {
-            auto wrapc = [&](int q) { return q < 0 ? q + nc : (q >= nc ? q - nc : q); };
-#pragma unroll
-            for (int it = 0; it < IC; ++it) {
-                const int i = tid + it * 256;
-                if (i < 4 * CN) {
-                    const int f = i / CN, j = i - f * CN, r = j / CW, c = j - r * CW;
-                    vc[it] = a.xc[f * ncc + wrapc(cr0 - 2 + r) * nc + wrapc(cc0 - 2 + c)];
-                }
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 256;
-            if (i < kFSN) {
-                const int sr = i / kFSW, sc = i - sr * kFSW;
-                const int32_t k = P.wrap(rb + sr) * n + P.wrap(cb + sc);
-                v[it][0] = P.cell[k];
-                if constexpr (!INIT) {
-#pragma unroll
-                    for (int f = 0; f < 4; ++f) v[it][1 + f] = a.x_in[f * nn + k];
-                }
-            }
-        }
-        if constexpr (PRO) {
-#pragma unroll
-            for (int it = 0; it < IC; ++it)
-                if (tid + it * 256 < 4 * CN) xl[tid + it * 256] = vc[it];
-            __syncthreads();
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 256;
-            if (i < kFSN) {
-                ts[i] = v[it][0];
-                if constexpr (!INIT) {
-                    if constexpr (PRO) {   // x_in + P_0 xc: k_mg_transfer_spmv's prolongation and EpiAdd's sum
-                        const int sr = i / kFSW, sc = i - sr * kFSW;
-                        const int gr = P.wrap(rb + sr), gc = P.wrap(cb + sc);
-                        const bool inner = g1_inner(cr0, cc0, kFTH / 2, kFTW / 2, nc);   // (window coordinates)
-#pragma unroll
-                        for (int f = 0; f < 4; ++f) {
-                            const double pc =
-                                inner ? ((f & 1) ? g1_p_in<MPBP_MG_NODE, MPBP_MG_CELL>(xl + f * CN, sr, sc)
-                                                 : g1_p_in<MPBP_MG_CELL, MPBP_MG_NODE>(xl + f * CN, sr, sc))
-                                      : ((f & 1) ? g1_p<MPBP_MG_NODE, MPBP_MG_CELL>(xl + f * CN, gr, gc, nc, cr0 - 2, cc0 - 2)
-                                                 : g1_p<MPBP_MG_CELL, MPBP_MG_NODE>(xl + f * CN, gr, gc, nc, cr0 - 2, cc0 - 2));
-                            xs[f * kFSN + i] = pc + v[it][1 + f];
-                        }
-                    } else {
-#pragma unroll
-                        for (int f = 0; f < 4; ++f) xs[f * kFSN + i] = v[it][1 + f];
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
-    const TTileT<kFSW> tt{ts, rb, cb};
-    const TTileWT<kFSW> tw{ts, rb, cb, n};
-    const XTileT<kFSW, kFSH> xa{xs, rb, cb};
-    const XTileT<kFAW, kFAH> xb{xl, rb + 1, cb + 1};
-    // level A at virtual cell (vr, vc): its x (xn), d (dA) and the reciprocal diagonals (rd)
-    auto level_a = [&](int vr, int vc, double* dA, double* rd) {
-        const int si = (vr - rb - 1) * kFAW + (vc - cb - 1);
-        const int gr = P.wrap(vr), gc = P.wrap(vc);
-        const int32_t k = gr * n + gc;
-        double bv[4];
-        typename BS::Q q{};
-        if constexpr (BS::on) q = bs.load(gr, gr, gc);
-        else {
-#pragma unroll
-            for (int f = 0; f < 4; ++f) bv[f] = a.b[f * nn + k];
-        }
-        const FStencilDev::Stage sg{{P.uface[k], P.vface[k]}};
-        if constexpr (INIT) {
-            P.rdiag4(vr, vc, tt, sg, rd);
-#pragma unroll
-            for (int f = 0; f < 4; ++f) {
-                const double bf = BS::on ? bs.b(f, gr, gc, gc, tw, q) : bv[f];
-                const double x0 = a.c2a * bf * rd[f];
-                xl[f * kFAN + si] = x0;
-                dA[f] = x0;
-            }
-        } else {
-            double acc[4];
-            P.rows4(vr, vc, tt, xa, FStencilDev::Cell{{sg.face[0], sg.face[1]}}, acc, rd);
-#pragma unroll
-            for (int f = 0; f < 4; ++f) {
-                const double bf = BS::on ? bs.b(f, gr, gc, gc, tw, q) : bv[f];
-                const double z = (bf - acc[f]) * rd[f];
-                const double dprev = a.dzero ? 0.0 : a.d_in[f * nn + k];
-                const double dn = a.c1a * dprev + a.c2a * z;
-                xl[f * kFAN + si] = xa.X(f, vr, vc) + dn;
-                dA[f] = dn;
-            }
-        }
-    };
-    const int lc = tid & 63, lr = tid >> 6;
-    double dA0[4], dA1[4], rd0[4], rd1[4];
-    level_a(r0 + lr, c0 + lc, dA0, rd0);
-    level_a(r0 + 4 + lr, c0 + lc, dA1, rd1);
-    // the halo ring: rows -1 and kFTH (66 cells each), columns -1 and kFTW of rows 0 .. kFTH-1: 148 cells
-    constexpr int kRing = 2 * (kFTW + 2) + 2 * kFTH;
-    if (tid < kRing) {
-        int hr, hc;
-        if (tid < 2 * (kFTW + 2)) {
-            const int j = tid < kFTW + 2 ? tid : tid - (kFTW + 2);
-            hr = tid < kFTW + 2 ? r0 - 1 : r0 + kFTH;
-            hc = c0 - 1 + j;
-        } else {
-            const int j = tid - 2 * (kFTW + 2);
-            hr = r0 + (j >> 1);
-            hc = (j & 1) ? c0 + kFTW : c0 - 1;
-        }
-        double dh[4], rh[4];
-        level_a(hr, hc, dh, rh);
-    }
-    __syncthreads();
-    // level B on the tile's own cells
-    auto level_b = [&](int vr, int vc, const double* dA, const double* rdA) {
-        if (vr >= n || vc >= n) return;   // a tile past the grid's last row / column
-        const int32_t k = vr * n + vc;
-        const FStencilDev::Cell cl{{P.uface[k], P.vface[k]}};
-        double acc[4], rdx[4];
-        P.template rows4<false>(vr, vc, tt, xb, cl, acc, rdx);
-        typename BS::Q q{};
-        if constexpr (BS::on) q = bs.load(vr, vr, vc);
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const double bf = BS::on ? bs.b(f, vr, vc, vc, tw, q) : a.b[f * nn + k];
-            const double z = (bf - acc[f]) * rdA[f];
-            const double dn = a.c1b * dA[f] + a.c2b * z;
-            const int32_t o = f * nn + k;
-            if constexpr (SD) a.d_out[o] = dn;
-            const double x = xb.X(f, vr, vc) + dn;
-            a.x_out[o] = SUB ? a.sub[o] - x : x;
-        }
-    };
-    level_b(r0 + lr, c0 + lc, dA0, rd0);
-    level_b(r0 + 4 + lr, c0 + lc, dA1, rd1);
-}
-
-template <bool INIT, bool SUB, bool SD, class BS>
-int launch_ftile_t(const FStencilFast& P, const FTile& a, hipStream_t st, const BS& bs) {
-    const int64_t tiles = (int64_t)((P.n + kFTW - 1) / kFTW) * ((P.n + kFTH - 1) / kFTH);
-    if constexpr (!INIT && !BS::on) {
-        if (a.xc) {
-            k_ftile<INIT, SUB, SD, BS, true><<<(unsigned)tiles, 256, 0, st>>>(P, a, bs);
-            MPBP_HIP(hipGetLastError());
-            return MPBP_OK;
-        }
-    }
-    k_ftile<INIT, SUB, SD, BS><<<(unsigned)tiles, 256, 0, st>>>(P, a, bs);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-// INIT: level A = x0, level B = sweep 1 (the solve's first two updates); else sweeps s, s + 1.  One GPU, whole grid.
-// Grids whose cells a tile and its staged halo wrap onto at most once each way.
-inline bool ftile_ok(int n) { return n >= kFTW + kFTH + 4; }
-template <bool INIT, class BS = BNone>
-int launch_ftile(const FStencilDev& Pd, const FTile& a, hipStream_t st, const BS& bs = BS{}) {
-    const FStencilFast P{Pd};
-    if (P.h != 0 || P.which != 0 || !ftile_ok(P.n)) return set_error(MPBP_ERR_ARG, "ftile: one GPU, whole grid, n >= 76");
-    if (!a.x_out || (!INIT && (!a.x_in || (!a.d_in && !a.dzero) || a.x_in == a.x_out)) || (!BS::on && !a.b) ||
-        (a.d_out && (a.d_out == a.d_in || a.d_out == a.x_in)) || (a.xc && (INIT || BS::on || (P.n & 1))))
-        return set_error(MPBP_ERR_ARG, "ftile: bad vectors");
-    const bool sub = a.sub != nullptr, sd = a.d_out != nullptr;
-    return sub ? (sd ? launch_ftile_t<INIT, true, true>(P, a, st, bs) : launch_ftile_t<INIT, true, false>(P, a, st, bs))
-               : (sd ? launch_ftile_t<INIT, false, true>(P, a, st, bs) : launch_ftile_t<INIT, false, false>(P, a, st, bs));
-}
-
-// ---- a whole tolerance-mode F Chebyshev solve in one launch (k_fsolve) ----
-// x = F^-1 b by K = H + 1 Chebyshev-Jacobi updates from x0 = 0 (the first is the pointwise x0 = d0 = c2_0 b / diag),
-// on the 64 x 8 tiles of k_ftile: thn is staged over the tile plus H + 1 halo cells, level 0 builds x0 over the tile
-// plus H, and level l = 1 .. H recomputes the tile plus H - l from level l - 1 (LDS ping-pong), the last writing x.
-// Every cell a workgroup computes has one owning lane for all its levels: the lane's two tile cells (as k_ftile) and
-// cell t of each halo ring r = 1 .. H (140 + 8 r cells, lane t < that), so its d, b, faces and reciprocal diagonals
-// stay in that lane's registers from level 0 on.  Each level performs the IEEE operations of the marching kernels'
-// tolerance-mode rows and updates: bit-identical to k_ftile<INIT> + k_ftile pair (H = 3) or + k_ftile sweep.  HBM:
-// b (or x_p), thn, faces in, x out once -- against x, d, b re-read per launch by the two-launch solve.
-template <int H>
-struct FsTile {
-    static constexpr int RW = kFTW + 2 * H, RH = kFTH + 2 * H, N = RW * RH;   // x levels: the tile + H
-    static constexpr int TW = RW + 2, TH = RH + 2, TN = TW * TH;             // thn: the tile + H + 1
-};
-struct FSolve {
-    const double* b;      // BNone: the right-hand side
-    const double* sub;    // the result is sub - x when set
-    double* x_out;
-    double c2_0;
-    double c1[4], c2[4];  // updates 1 .. H
-};
-// ring r's cell j: rows r0 - r and r0 + TH - 1 + r (all 64 + 2r columns), then columns c0 - r and c0 + TW - 1 + r of
-// the rows between
-__device__ inline void fs_ring_cell(int r, int j, int r0, int c0, int& vr, int& vc) {
-    const int w = kFTW + 2 * r;
-    if (j < 2 * w) {
-        vr = j < w ? r0 - r : r0 + kFTH - 1 + r;
-        vc = c0 - r + (j < w ? j : j - w);
-    } else {
-        const int k = j - 2 * w;
-        vr = r0 - r + 1 + (k >> 1);
-        vc = (k & 1) ? c0 + kFTW - 1 + r : c0 - r;
-    }
-}
-
-// PART (row partition, the CA schedule): the tiles cover the owned rows and P.ext ghost rows each side; b and x are
-// in the partition's ghost layout (P.xrow, P.out_row), the thn tables global.  Rows past b's ghost depth (padding of
-// the last tile row and its halo, which no output reads) load a clamped row.
-template <int H, bool SUB, bool PART, class BS>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) MPBP_LDS_READS
-k_fsolve(FStencilFast P, FSolve a, BS bs) {
-    using T = FsTile<H>;
-    constexpr int NT = 2;       // tile cells per lane
-    constexpr int NSL = H + 2;  // owned cells per lane: the tile's two (rows lr, lr + 4), then ring r at slot 1 + r
-    constexpr int NS = H + 1;   // ... with updates after x0 (ring H only needs x0)
-    constexpr int PW = T::RW + 1, PN = PW * (T::RH + 1);   // BS: x_p over the tile + H, + its west / north neighbours
-    __shared__ double ts[T::TN];
-    __shared__ double xa[4 * T::N], xb[4 * T::N];
-    __shared__ double ps[BS::on ? PN : 1];
-    const int n = P.n, nn = n * n;
-    const int tx = (n + kFTW - 1) / kFTW;
-    const int bk = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int lo = PART ? P.r0 - P.ext : 0, hi = PART ? P.r0 + P.L + P.ext : n;   // output rows [lo, hi)
-    const int r0 = lo + (bk / tx) * kFTH, c0 = (bk % tx) * kFTW;
-    const int rbt = r0 - H - 1, cbt = c0 - H - 1, rb = r0 - H, cb = c0 - H;
-    const int tid = threadIdx.x;
-    // a row of the input layouts: the virtual row itself (one GPU: wrapped) or, clamped to the ghost depth, local
-    auto in_row = [&](int vr, int h) {
-        if constexpr (PART) {
-            const int lr = vr - P.r0;
-            return lr < -h ? -h : (lr >= P.L + h ? P.L + h - 1 : lr);
-        } else {
-            return P.wrap(vr);
-        }
-    };
-    {
-        constexpr int IT = (T::TN + 255) / 256;
-        double v[IT];
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 256;
-            if (i < T::TN) {
-                const int sr = i / T::TW, sc = i - sr * T::TW;
-                v[it] = P.cell[P.wrap(rbt + sr) * n + P.wrap(cbt + sc)];
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 256;
-            if (i < T::TN) ts[i] = v[it];
-        }
-    }
-    if constexpr (BS::on) {
-        constexpr int IT = (PN + 255) / 256;
-        double v[IT];
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 256;
-            if (i < PN) {
-                const int sr = i / PW, sc = i - sr * PW;
-                const int pr = in_row(rb - 1 + sr, PART ? bs.h : 0);
-                v[it] = bs.xp[(PART ? ext_row(1, 0, pr, P.L, bs.h, n) : pr * n) + P.wrap(cb - 1 + sc)];
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 256;
-            if (i < PN) ps[i] = v[it];
-        }
-    }
-    const int lr = tid >> 6, lc = tid & 63;
-    // the owned cells and their rings (0: a tile cell; ring r lives through level H - r)
-    int cr[NSL], cc[NSL], rr[NSL];
-    bool own[NSL];
-#pragma unroll
-    for (int m = 0; m < NT; ++m) {
-        cr[m] = r0 + lr + 4 * m; cc[m] = c0 + lc; own[m] = true; rr[m] = 0;
-    }
-#pragma unroll
-    for (int r = 1; r <= H; ++r) {
-        own[1 + r] = tid < 140 + 8 * r;
-        rr[1 + r] = r;
-        fs_ring_cell(r, own[1 + r] ? tid : 0, r0, c0, cr[1 + r], cc[1 + r]);
-    }
-    // every owned cell's faces and b (BNone) are loaded here, behind the staging loads and ahead of the barrier: one
-    // global-memory latency for the whole level 0 instead of one per cell
-    double fl[NSL][2], bl[BS::on ? 1 : NSL][4];
-#pragma unroll
-    for (int sl = 0; sl < NSL; ++sl) {
-        if (!own[sl]) continue;
-        const int gr = P.wrap(cr[sl]), gc = P.wrap(cc[sl]);
-        const int32_t k = gr * n + gc;
-        fl[sl][0] = P.uface[k];
-        fl[sl][1] = P.vface[k];
-        if constexpr (!BS::on) {
-            const int br = in_row(cr[sl], P.h);
-#pragma unroll
-            for (int f = 0; f < 4; ++f) bl[sl][f] = a.b[(PART ? ext_row(4, f, br, P.L, P.h, n) : (f * n + br) * n) + gc];
-        }
-    }
-    __syncthreads();
-    const TTileT<T::TW> tt{ts, rbt, cbt};
-    double d[NS][4], rd[NS][4], bv[NS][4], fc[NS][2];
-    // level 0: x0 = d0 = c2_0 b / diag over the tile + H
-#pragma unroll
-    for (int sl = 0; sl < NSL; ++sl) {
-        if (!own[sl]) continue;
-        const int vr = cr[sl], vc = cc[sl];
-        const int gr = P.wrap(vr), gc = P.wrap(vc);
-        const FStencilDev::Stage sg{{fl[sl][0], fl[sl][1]}};
-        double b4[4], r4[4];
-        P.rdiag4(vr, vc, tt, sg, r4);
-        if constexpr (BS::on) {   // b = G x_p, x_p and thn from LDS at virtual coordinates
-            const int pi = (vr - rb + 1) * PW + (vc - cb + 1);
-            const typename BS::Q q{ps[pi], ps[pi - 1], ps[pi - PW]};
-#pragma unroll
-            for (int f = 0; f < 4; ++f) b4[f] = bs.b_at(f, vr, vc, gc == 0, gr == 0, tt, q);
-        } else {
-#pragma unroll
-            for (int f = 0; f < 4; ++f) b4[f] = bl[sl][f];
-        }
-        const int si = (vr - rb) * T::RW + (vc - cb);
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const double x0 = a.c2_0 * b4[f] * r4[f];
-            xa[f * T::N + si] = x0;
-            if (sl < NS) {
-                d[sl][f] = x0;
-                rd[sl][f] = r4[f];
-                bv[sl][f] = b4[f];
-            }
-        }
-        if (sl < NS) {
-            fc[sl][0] = sg.face[0];
-            fc[sl][1] = sg.face[1];
-        }
-    }
-    // levels 1 .. H
-    double* cur = xa;
-    double* nxt = xb;
-    double sv[NT][4];   // SUB: the tile cells' sub entries, loaded at the start of level H (its stencil work hides them)
-#pragma unroll
-    for (int l = 1; l <= H; ++l) {
-        __syncthreads();
-        const XTileT<T::RW, T::RH> xt{cur, rb, cb};
-        const double c1 = a.c1[l - 1], c2 = a.c2[l - 1];
-        if constexpr (SUB) {
-            if (l == H) {
-#pragma unroll
-                for (int m = 0; m < NT; ++m) {
-                    const int vr = cr[m], vc = cc[m];
-                    if (vr >= hi || vc >= n) continue;
-#pragma unroll
-                    for (int f = 0; f < 4; ++f)
-                        sv[m][f] = a.sub[PART ? P.out_row(f, vr - P.r0, vc) : f * nn + vr * n + vc];
-                }
-            }
-        }
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) {
-            if (sl >= NT && (!own[sl] || rr[sl] > H - l)) continue;   // ring r lives through level H - r
-            const int vr = cr[sl], vc = cc[sl];
-            if (l == H && (vr >= hi || vc >= n)) continue;            // a tile past the last row / column
-            double acc[4], rdx[4];
-            P.template rows4<false>(vr, vc, tt, xt, FStencilDev::Cell{{fc[sl][0], fc[sl][1]}}, acc, rdx);
-            const int si = (vr - rb) * T::RW + (vc - cb);
-#pragma unroll
-            for (int f = 0; f < 4; ++f) {
-                const double z = (bv[sl][f] - acc[f]) * rd[sl][f];
-                const double dn = c1 * d[sl][f] + c2 * z;
-                const double x = cur[f * T::N + si] + dn;
-                if (l < H) {
-                    nxt[f * T::N + si] = x;
-                    d[sl][f] = dn;
-                } else {
-                    const int32_t o = PART ? P.out_row(f, vr - P.r0, vc) : f * nn + vr * n + vc;
-                    if constexpr (SUB) a.x_out[o] = sv[sl < NT ? sl : 0][f] - x;   // (level H: tile cells only)
-                    else a.x_out[o] = x;
-                }
-            }
-        }
-        double* t = cur;
-        cur = nxt;
-        nxt = t;
-    }
-}
-
-// Grids a tile's staged thn (tile + H + 1 each side) wraps onto at most once.
-template <int H>
-inline bool fsolve_ok_n(int n) { return n >= FsTile<H>::TW && n >= FsTile<H>::TH; }
-template <int H, bool PART, class BS>
-int launch_fsolve_t(const FStencilFast& P, const FSolve& a, hipStream_t st, const BS& bs) {
-    const int rows = PART ? P.L + 2 * P.ext : P.n;
-    const int64_t tiles = (int64_t)((P.n + kFTW - 1) / kFTW) * ((rows + kFTH - 1) / kFTH);
-    if (a.sub) k_fsolve<H, true, PART, BS><<<(unsigned)tiles, 256, 0, st>>>(P, a, bs);
-    else k_fsolve<H, false, PART, BS><<<(unsigned)tiles, 256, 0, st>>>(P, a, bs);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-// ---- k_fsolve on narrower tiles with the halo rings spread evenly over the waves (kernel option f_solve_tile) ----
-// The same whole-solve launch as k_fsolve, the same operations per cell and level (bit-identical), on a TW x TH tile
-// (32 x 16: 10 % fewer cell-levels than 64 x 8 -- 2 680 instead of 2 968 per 512 outputs at H = 3 -- because the
-// halo rings are shorter).  A level's time is set by the wave with the most owned cells it updates, so ring r's cells
-// are dealt out in four equal contiguous runs, one per wave: rings 1 .. H - 1 share one slot (lanes 0 .. 51 of every
-// wave at 32 x 16, H = 3), ring H (x0 only) a second.  Per wave and level: x0 on 4 cells (k_fsolve 64 x 8: 5), then
-// 3, 3, 2 stencil cells (4, 3, 2), and three cells' state in registers instead of four.  The level-invariant part of
-// the rows is computed once: the node averages K(r, c) into an LDS table (FStencilFast::coeffs' kc / ks / ke are
-// K(r, c), K(r + 1, c), K(r, c + 1), the same sums in the same order), and each owned cell keeps its XI couplings and
-// identity weights in registers (in place of its two face values), so a level reads 6 coefficients instead of 8
-// thn values and skips ~27 of the row's ~115 fp64 operations.  Level 0 reads the table too (one more barrier, no node
-// average computed twice); thn, x_p and the table are staged by wave-uniform rows, and an owned cell's global and LDS
-// indices all derive from one wrapped (row, column) pair and one tile-relative (dr, dc) pair.  (An in-place variant -- one x image, a second barrier
-// per level, 34 KB of LDS for three workgroups per CU -- spilled ~700 B per lane at the 168-VGPR cap and ran 4.5x
-// slower: removed.)
-template <int TW, int TH, int H>
-struct FsGeom {
-    static constexpr int RW = TW + 2 * H, RH = TH + 2 * H, N = RW * RH;   // x levels: the tile + H
-    static constexpr int TSW = RW + 2, TSH = RH + 2, TSN = TSW * TSH;     // thn: the tile + H + 1
-    static constexpr int NT = TW * TH / 256;                             // tile cells per lane
-    static constexpr int ring(int r) { return 2 * TW + 2 * TH + 8 * r - 4; }
-    static constexpr int q(int r) { return ring(r) / 4; }               // ring r's cells per wave
-    static constexpr int qa() {                                          // slot A: rings 1 .. H - 1, per wave
-        int s = 0;
-        for (int r = 1; r < H; ++r) s += q(r);
-        return s;
-    }
-};
-template <int TW, int TH>
-__device__ inline void fs_ring_cell_t(int r, int j, int r0, int c0, int& vr, int& vc) {
-    const int w = TW + 2 * r;
-    if (j < 2 * w) {
-        vr = j < w ? r0 - r : r0 + TH - 1 + r;
-        vc = c0 - r + (j < w ? j : j - w);
-    } else {
-        const int k = j - 2 * w;
-        vr = r0 - r + 1 + (k >> 1);
-        vc = (k & 1) ? c0 + TW - 1 + r : c0 - r;
-    }
-}
-// the same cell of ring r (a constant where it is called) as offsets from the corner of the tile + h
-template <int TW, int TH>
-__device__ inline void fs_ring_rel(int r, int j, int h, int& dr, int& dc) {
-    const int w = TW + 2 * r, k = j - 2 * w;
-    const bool top = j < w, row = j < 2 * w;
-    dr = h + (row ? (top ? -r : TH - 1 + r) : 1 - r + (k >> 1));
-    dc = h + (row ? (top ? j : j - w) - r : ((k & 1) ? TW - 1 + r : -r));
-}
-// base[off / 8] with base wave-uniform and off a 32-bit byte offset: the scalar-base form of the global access
-template <class V>
-__device__ inline V* at_off(V* base, uint32_t off) { return (V*)((const char*)base + off); }
-__device__ inline double ld_off(const double* base, uint32_t off) { return *at_off(base, off); }
-template <int W>
-struct TRelT {   // staged thn around one cell: t points at it, W columns per staged row
-    const double* t;
-    __device__ double T(int sph, int r, int c) const {
-        const double v = t[r * W + c];
-        return sph ? 1.0 - v : v;
-    }
-};
-template <int W, int N>
-struct XRelT {   // 4 fields ([4][N], W columns per row) around one cell: x points at its field-0 entry
-    const double* x;
-    __device__ double X(int f, int r, int c) const { return x[f * N + r * W + c]; }
-};
-template <int TW, int TH, int H, bool SUB, bool PART, class BS>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) MPBP_LDS_READS
-k_fsolve_w(FStencilFast P, FSolve a, BS bs) {
-    using T = FsGeom<TW, TH, H>;
-    static_assert(TW * TH == 256 * T::NT && TW % 32 == 0, "whole rows of 32 lanes, NT cells per lane");
-    static_assert((2 * TW + 2 * TH - 4) % 4 == 0, "every ring splits into four equal runs");
-    static_assert(T::qa() <= 64 && T::q(H) <= 64, "one ring slot for rings 1 .. H - 1 and one for ring H");
-    constexpr int NT = T::NT;
-    constexpr int NSL = NT + 2;   // owned cells per lane: NT tile cells, slot A (rings 1 .. H - 1), slot B (ring H)
-    constexpr int NS = NT + 1;    // ... with updates after x0 (ring H only needs x0)
-    constexpr int PW = T::RW + 1, PH = T::RH + 1, PN = PW * PH;   // BS: x_p over the tile + H, + its west / north neighbours
-    // node averages K(r, c) of the tile + H, + 1 row / column: ks / ke of every level-0 cell, ring H included
-    constexpr int KW = T::RW + 1, KN = KW * (T::RH + 1);
-    static_assert(T::TSW <= 64 && PW == KW, "a staged row is one wave's lanes; x_p's window and the K table share indices");
-    __shared__ double ts[T::TSN];
-    __shared__ double kt[KN];
-    __shared__ double xa[4 * T::N], xb[4 * T::N];
-    __shared__ double ps[BS::on ? PN : 1];
-    const int n = P.n, nn = n * n;
-    const int tx = (n + TW - 1) / TW;
-    const int bk = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int lo = PART ? P.r0 - P.ext : 0, hi = PART ? P.r0 + P.L + P.ext : n;   // output rows [lo, hi)
-    const int r0 = lo + (bk / tx) * TH, c0 = (bk % tx) * TW;
-    const int rbt = r0 - H - 1, cbt = c0 - H - 1, rb = r0 - H, cb = c0 - H;
-    const int tid = threadIdx.x;
-    auto in_row = [&](int vr, int h) {
-        if constexpr (PART) {
-            const int lr = vr - P.r0;
-            return lr < -h ? -h : (lr >= P.L + h ? P.L + h - 1 : lr);
-        } else {
-            return P.wrap(vr);
-        }
-    };
-    // Staging by rows: wave w takes staged rows w, w + 4, ..., lane l column l.  A row's wrapped global base is
-    // scalar work, the wrapped column is the lane's own for every row (x_p's window starts at the same (rbt, cbt)), and
-    // an iteration is one load or one LDS store at an immediate offset from the lane's base.
-    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6) & 3;
-    const uint32_t gcs = 8u * (uint32_t)P.wrap(cbt + (lane < T::TSW ? lane : 0));   // (byte offsets: n n 8 < 2^32)
-    if (lane < T::TSW) {
-        constexpr int IT = (T::TSH + 3) / 4;
-        double v[IT];
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int sr = wv + 4 * it;
-            if (sr < T::TSH) v[it] = ld_off(P.cell + P.wrap(rbt + sr) * n, gcs);
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int sr = wv + 4 * it;
-            if (sr < T::TSH) ts[sr * T::TSW + lane] = v[it];
-        }
-    }
-    if constexpr (BS::on) {
-        if (lane < PW) {
-            constexpr int IT = (PH + 3) / 4;
-            double v[IT];
-#pragma unroll
-            for (int it = 0; it < IT; ++it) {
-                const int sr = wv + 4 * it;
-                if (sr < PH) {
-                    const int pr = in_row(rbt + sr, PART ? bs.h : 0);
-                    v[it] = ld_off(bs.xp + (PART ? ext_row(1, 0, pr, P.L, bs.h, n) : pr * n), gcs);
-                }
-            }
-#pragma unroll
-            for (int it = 0; it < IT; ++it) {
-                const int sr = wv + 4 * it;
-                if (sr < PH) ps[sr * PW + lane] = v[it];
-            }
-        }
-    }
-    // owned cells at (dr, dc) from the corner (rb, cb) of the tile + H: one LDS index per cell, neighbours at
-    // immediate offsets (xi: the x levels, xi + dr: the K table and x_p, xi + 2 dr + TSW + 1: thn)
-    int dr[NSL], dc[NSL];
-#pragma unroll
-    for (int m = 0; m < NT; ++m) {   // tile cell m: row (tid / TW) + m (256 / TW), column tid % TW
-        dr[m] = H + tid / TW + m * (256 / TW); dc[m] = H + tid % TW;
-    }
-    // slot A: rings 1 .. H - 1 in consecutive lane ranges (the ring is the range's: compile time); slot B: ring H
-    int rA = 0;   // slot A's ring, 0: none
-    dr[NT] = H; dc[NT] = H;
-    {
-        int base = 0;
-#pragma unroll
-        for (int q = 1; q < H; ++q) {
-            if (lane >= base && lane < base + T::q(q)) {
-                fs_ring_rel<TW, TH>(q, wv * T::q(q) + lane - base, H, dr[NT], dc[NT]);
-                rA = q;
-            }
-            base += T::q(q);
-        }
-    }
-    const bool ownB = lane < T::q(H);
-    fs_ring_rel<TW, TH>(H, ownB ? wv * T::q(H) + lane : 0, H, dr[NT + 1], dc[NT + 1]);
-    auto own = [&](int sl) { return sl < NT || (sl == NT ? rA != 0 : ownB); };
-    // one wrapped (gr, gc) and k = gr n + gc per cell: faces, b, sub and the output (a tile cell inside the grid is
-    // its own wrapped cell) index from it: a 32-bit byte offset from the field's base (n n 8 < 2^32)
-    double fl[NSL][2], bl[BS::on ? 1 : NSL][4];
-    uint32_t kg[NSL];
-    bool ww[NSL], wn[NSL], outok[NT];
-#pragma unroll
-    for (int sl = 0; sl < NSL; ++sl) {
-        if (!own(sl)) continue;
-        const int vr = rb + dr[sl], vc = cb + dc[sl];
-        // (a tile cell's column is never negative, nor its row on the whole grid)
-        const int gr = !PART && sl < NT ? (vr >= n ? vr - n : vr) : P.wrap(vr);
-        const int gc = sl < NT ? (vc >= n ? vc - n : vc) : P.wrap(vc);
-        kg[sl] = 8u * (uint32_t)(gr * n + gc);
-        ww[sl] = gc == 0;
-        wn[sl] = gr == 0;
-        if (sl < NT) outok[sl < NT ? sl : 0] = vr < hi && vc < n;   // else a tile past the last row / column
-        fl[sl][0] = ld_off(P.uface, kg[sl]);
-        fl[sl][1] = ld_off(P.vface, kg[sl]);
-        if constexpr (!BS::on) {
-            if constexpr (PART) {
-                const int br = in_row(vr, P.h);
-#pragma unroll
-                for (int f = 0; f < 4; ++f) bl[sl][f] = a.b[ext_row(4, f, br, P.L, P.h, n) + gc];
-            } else {
-#pragma unroll
-                for (int f = 0; f < 4; ++f) bl[sl][f] = ld_off(a.b + (size_t)f * nn, kg[sl]);
-            }
-        }
-    }
-    __syncthreads();
-    // the node averages every level reads (FStencilFast::coeffs' kc of cell (r, c), ks of (r - 1, c), ke of (r, c - 1):
-    // the same sum in the same order), computed once, by rows as the staging; level 0 reads them too
-    if (lane < KW) {
-        constexpr int IK = (T::RH + 1 + 3) / 4;
-#pragma unroll
-        for (int it = 0; it < IK; ++it) {
-            const int kr = wv + 4 * it;
-            if (kr < T::RH + 1) {
-                const double* t = ts + kr * T::TSW + lane;   // thn(rb + kr - 1, cb + lane - 1)
-                kt[kr * KW + lane] = 0.25 * ((t[0] + t[1]) + (t[T::TSW] + t[T::TSW + 1]));
-            }
-        }
-    }
-    __syncthreads();
-    // per owned cell: d, its reciprocal diagonals, b, and the level-invariant row terms (XI couplings xu / xv, weights)
-    double d[NS][4], rd[NS][4], bv[NS][4], kx[NS][2];
-    typename FStencilFast::W4 wt[NS];
-    // level 0: x0 = d0 = c2_0 b / diag over the tile + H
-#pragma unroll
-    for (int sl = 0; sl < NSL; ++sl) {
-        if (!own(sl)) continue;
-        const int si = dr[sl] * T::RW + dc[sl], ki = si + dr[sl];
-        const double* t = ts + (ki + dr[sl] + T::TSW + 1);   // thn at the cell
-        const FStencilDev::Cell cl{{fl[sl][0], fl[sl][1]}};
-        const double tw = t[-1], tc = t[0], tn = t[-T::TSW];
-        const typename FStencilFast::Co k = P.coeffs_k(tw, tc, tn, tw + tc, kt[ki], kt[ki + KW], kt[ki + 1]);
-        const typename FStencilFast::W4 w = P.weights(cl);
-        double b4[4], r4[4];
-        P.rdiag4_co(k, w, r4);
-        if constexpr (BS::on) {
-            const int pi = ki + PW + 1;
-            const typename BS::Q q{ps[pi], ps[pi - 1], ps[pi - PW]};
-#pragma unroll
-            for (int f = 0; f < 4; ++f) b4[f] = bs.b_at(f, 0, 0, ww[sl], wn[sl], TRelT<T::TSW>{t}, q);
-        } else {
-#pragma unroll
-            for (int f = 0; f < 4; ++f) b4[f] = bl[sl][f];
-        }
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const double x0 = a.c2_0 * b4[f] * r4[f];
-            xa[f * T::N + si] = x0;
-            if (sl < NS) {
-                d[sl][f] = x0;
-                rd[sl][f] = r4[f];
-                bv[sl][f] = b4[f];
-            }
-        }
-        if (sl < NS) {
-            kx[sl][0] = k.xu;
-            kx[sl][1] = k.xv;
-            wt[sl] = w;
-        }
-    }
-    double* cur = xa;
-    double* nxt = xb;
-    double sv[NT][4];
-#pragma unroll
-    for (int l = 1; l <= H; ++l) {
-        __syncthreads();
-        const double c1 = a.c1[l - 1], c2 = a.c2[l - 1];
-        // tile cell m's entry of field f in the output's layout (the row partition keeps its layout's own addressing)
-        auto out_at = [&](auto* v, int m, int f) {
-            if constexpr (PART) return v + P.out_row(f, rb + dr[m] - P.r0, cb + dc[m]);
-            else return at_off(v + (size_t)f * nn, kg[m]);
-        };
-        if constexpr (SUB) {
-            if (l == H) {
-#pragma unroll
-                for (int m = 0; m < NT; ++m) {
-                    if (!outok[m]) continue;
-#pragma unroll
-                    for (int f = 0; f < 4; ++f) sv[m][f] = *out_at(a.sub, m, f);
-                }
-            }
-        }
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) {
-            if (sl >= NT && (l == H || rA == 0 || rA > H - l)) continue;   // ring r lives through level H - r
-            if (l == H && !outok[sl < NT ? sl : 0]) continue;
-            const int si = dr[sl] * T::RW + dc[sl], ki = si + dr[sl];
-            const double* t = ts + (ki + dr[sl] + T::TSW + 1);
-            typename FStencilFast::Co k;
-            k.w = t[-1];
-            k.c = t[0];
-            k.nn = t[-T::TSW];
-            k.kc = kt[ki];
-            k.ks = kt[ki + KW];
-            k.ke = kt[ki + 1];
-            k.xu = kx[sl][0];
-            k.xv = kx[sl][1];
-            double acc[4];
-            P.rows4_co(0, 0, k, wt[sl], XRelT<T::RW, T::N>{cur + si}, acc);
-#pragma unroll
-            for (int f = 0; f < 4; ++f) {
-                const double z = (bv[sl][f] - acc[f]) * rd[sl][f];
-                const double dn = c1 * d[sl][f] + c2 * z;
-                if (l < H) {
-                    nxt[f * T::N + si] = cur[f * T::N + si] + dn;
-                    d[sl][f] = dn;
-                } else {
-                    const double x = cur[f * T::N + si] + dn;
-                    if constexpr (SUB) *out_at(a.x_out, sl < NT ? sl : 0, f) = sv[sl < NT ? sl : 0][f] - x;
-                    else *out_at(a.x_out, sl < NT ? sl : 0, f) = x;
-                }
-            }
-        }
-        double* t = cur;
-        cur = nxt;
-        nxt = t;
-    }
-}
-// Grids the narrow tile's staged thn (tile + H + 1 each side) wraps onto at most once.
-template <int TW, int TH, int H>
-inline bool fsolve_w_ok_n(int n) { return n >= FsGeom<TW, TH, H>::TSW && n >= FsGeom<TW, TH, H>::TSH; }
-template <int H, bool PART, class BS>
-int launch_fsolve_w(const FStencilFast& P, const FSolve& a, hipStream_t st, const BS& bs) {
-    constexpr int TW = 32, TH = 16;
-    const int rows = PART ? P.L + 2 * P.ext : P.n;
-    const int64_t tiles = (int64_t)((P.n + TW - 1) / TW) * ((rows + TH - 1) / TH);
-    if (a.sub) k_fsolve_w<TW, TH, H, true, PART, BS><<<(unsigned)tiles, 256, 0, st>>>(P, a, bs);
-    else k_fsolve_w<TW, TH, H, false, PART, BS><<<(unsigned)tiles, 256, 0, st>>>(P, a, bs);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-
-// K = 3 or 4 Chebyshev updates (x0 and H = K - 1 stencil sweeps); columns wrap at most once per tile.
-inline bool fsolve_ok(int K, int n) { return (K == 3 && fsolve_ok_n<2>(n)) || (K == 4 && fsolve_ok_n<3>(n)); }
-// One GPU, whole grid (P.h == 0), or a row partition's owned rows + P.ext ghost rows (P.which == 3), b's ghost depth
-// P.h >= P.ext + H (+ 1 for x_p's with GxBPart).
-template <class BS = BNone>
-int launch_fsolve(const FStencilDev& Pd, int K, const double* c1, const double* c2, const double* b, const double* sub,
-                  double* x_out, hipStream_t st, const BS& bs = BS{}) {
-    const FStencilFast P{Pd};
-    const bool part = P.h != 0;
-    int xp_h = 0;   // x_p's ghost depth (GxBPart)
-    if constexpr (BS::on) {
-        if (BS::part != part) return set_error(MPBP_ERR_ARG, "fsolve: G x_p's layout does not match F's");
-        if constexpr (BS::part) xp_h = bs.h;
-    }
-    if (!fsolve_ok(K, P.n) || (!part && P.which != 0) ||
-        (part && (P.which != 3 || P.h < P.ext + K - 1 || P.oh < P.ext || (BS::on && xp_h < P.ext + K))))
-        return set_error(MPBP_ERR_ARG, "fsolve: one GPU whole grid, or owned + ext rows with b ext + K - 1 deep");
-    if (!x_out || (!BS::on && !b) || x_out == b) return set_error(MPBP_ERR_ARG, "fsolve: bad vectors");
-    FSolve a{b, sub, x_out, c2[0], {}, {}};
-    for (int l = 1; l < K; ++l) {
-        a.c1[l - 1] = c1[l];
-        a.c2[l - 1] = c2[l];
-    }
-    constexpr bool bpart = BS::on && BS::part;   // GxBPart launches only the partitioned kernel, GxB the other
-    if (KO().f_solve_tile) {   // 32 x 16 tiles, rings spread over the waves, level-invariant terms cached
-        if (!(K == 3 ? fsolve_w_ok_n<32, 16, 2>(P.n) : fsolve_w_ok_n<32, 16, 3>(P.n)))
-            return set_error(MPBP_ERR_ARG, "fsolve: grid smaller than the 32 x 16 tile's staging");
-        if constexpr (BS::on) {
-            return K == 3 ? launch_fsolve_w<2, bpart>(P, a, st, bs) : launch_fsolve_w<3, bpart>(P, a, st, bs);
-        } else {
-            if (part) return K == 3 ? launch_fsolve_w<2, true>(P, a, st, bs) : launch_fsolve_w<3, true>(P, a, st, bs);
-            return K == 3 ? launch_fsolve_w<2, false>(P, a, st, bs) : launch_fsolve_w<3, false>(P, a, st, bs);
-        }
-    }
-    if constexpr (BS::on) {
-        return K == 3 ? launch_fsolve_t<2, bpart>(P, a, st, bs) : launch_fsolve_t<3, bpart>(P, a, st, bs);
-    } else {
-        if (part) return K == 3 ? launch_fsolve_t<2, true>(P, a, st, bs) : launch_fsolve_t<3, true>(P, a, st, bs);
-        return K == 3 ? launch_fsolve_t<2, false>(P, a, st, bs) : launch_fsolve_t<3, false>(P, a, st, bs);
-    }
-}
-
-// Sweeps s, s+1 of an F Chebyshev solve fused (k_march2, tolerance mode) over the rows P.which selects (0: the whole
-// grid, 3: owned + ext ghost rows; level A then covers ext + 1).  d_in may be d_out only when the pair does not store
-// its direction (SD false): level A reads d_in on its neighbours' rows and columns.
-template <bool SUB, bool SD, class BS>
-int launch_march2_t(const FStencilFast& P, const Fused2& a, hipStream_t st, const BS& bs) {
-    const int64_t chunks = march_chunks(P, KO().march_rows, march_capacity<k_march2<SUB, SD, BS>>());
-    if (chunks == 0) return MPBP_OK;
-    const int64_t strips = (P.n + kMB - 1) / kMB;
-    k_march2<SUB, SD, BS><<<(unsigned)(chunks * strips), kMB, 0, st>>>(P, a, (int)chunks, bs);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-template <class BS = BNone>
-int launch_march2(const FStencilDev& Pd, const Fused2& a, hipStream_t st, const BS& bs = BS{}) {
-    const FStencilFast P{Pd};
-    if (P.which == 1 || P.which == 2) return set_error(MPBP_ERR_ARG, "march2: interior / boundary row splits unsupported");
-    if (!a.x_in || !a.d_in || !a.x_out || a.x_in == a.x_out || (!BS::on && !a.b) || (a.d_out && a.d_out == a.d_in))
-        return set_error(MPBP_ERR_ARG, "march2: bad vectors");
-    const bool sub = a.sub != nullptr, sd = a.d_out != nullptr;
-    return sub ? (sd ? launch_march2_t<true, true>(P, a, st, bs) : launch_march2_t<true, false>(P, a, st, bs))
-               : (sd ? launch_march2_t<false, true>(P, a, st, bs) : launch_march2_t<false, false>(P, a, st, bs));
-}
-
-// The first inner sweep with x0 = c2 b / diag staged and diag rebuilt from thn (k_march_init).  BS = GxB: b is
-// W = G x_p recomputed per point (the second F solve of the apply).
-template <class S, class Epi, class BS = BNone>
-int launch_march_init(const S& P, const double* b, double c2, Epi epi, int rows_per_block, hipStream_t st,
-                      const BS& bs = BS{}) {
-    auto go = [&](const auto& e) {
-        using E = std::decay_t<decltype(e)>;
-        const int64_t chunks = march_chunks(P, rows_per_block, march_capacity<k_march_init<S, E, BS>>());
-        if (chunks == 0) return (int)MPBP_OK;
-        const int64_t strips = (P.n + kMB - 1) / kMB;
-        k_march_init<S, E, BS><<<(unsigned)(chunks * strips), kMB, 0, st>>>(P, b, c2, (int)chunks, e, bs);
-        MPBP_HIP(hipGetLastError());
-        return (int)MPBP_OK;
-    };
-    if constexpr (BS::on) return with_fixed_epi_bx<S::kFast>(epi, go);
-    else return with_fixed_epi<S::kFast>(epi, go);
-}
-
-template <class S, class XS, class Epi, class BS = BNone>
-int launch_march(const S& P, const XS& xs, Epi epi, int rows_per_block, hipStream_t st, const BS& bs = BS{}) {
-    auto go = [&](const auto& e) { return launch_march_fixed(P, xs, e, rows_per_block, st, bs); };
-    if constexpr (BS::on) return with_fixed_epi_bx<S::kFast>(epi, go);
-    else return with_fixed_epi<S::kFast>(epi, go);
-}
-
-// F row of field f at a cell (k_march policy).
-template <bool EDGE, class TA, class XA>
-__device__ inline double FStencilDev::row(int f, int gr, int gc, const TA& ta, const XA& xa, double* fd,
-                                          const Cell& cl) const {
-    return f_row<EDGE>(*this, f, gr, gc, ta, xa, fd, cl.face);
-}
-
-// The F policy with the parameter identities of f_row's M compiled in (the reference's own parameters,
-// d_u = -1 and eta_s = 1, solve.py:292-297 / apply.py:33-35): fewer fp64 multiplies per row, same bits.
-template <int M>
-struct FStencilDevM : FStencilDev {
-    template <bool EDGE, class TA, class XA>
-    __device__ double row(int f, int gr, int gc, const TA& ta, const XA& xa, double* fd, const Cell& cl) const {
-        return f_row<EDGE, TA, XA, false, M>(*this, f, gr, gc, ta, xa, fd, cl.face);
-    }
-    template <class TA>
-    __device__ double stage_diag(int f, int gr, int gc, const TA& ta, const Stage& s) const {
-        return f_stage_diag<M>(*this, f, gr, gc, ta, s);
-    }
-};
-
-// Calls fn with the F policy the plan's numerics select: the tolerance-mode rows (fast) or the bit-exact rows
-// specialised for P's parameter identities.
-template <class Fn>
-int with_f_identities(const FStencilDev& P, Fn&& fn);
-template <class Fn>
-int with_f_policy(const FStencilDev& P, bool fast, Fn&& fn) {
-    if (fast) return fn(FStencilFast{P});
-    return with_f_identities(P, fn);
-}
-
-// Calls fn with the F policy specialised for P's parameters (M = 0: none apply).
-template <class Fn>
-int with_f_identities(const FStencilDev& P, Fn&& fn) {
-    if (P.d_u == -1.0 && P.eta_s == 1.0) {
-        if (P.eta_n != 1.0 && P.pow2 && P.ce0 != 0.0 && __builtin_isfinite(P.ce0)) return fn(FStencilDevM<13>{P});
-        return P.eta_n == 1.0 ? fn(FStencilDevM<7>{P}) : fn(FStencilDevM<5>{P});
-    }
-    return fn(P);
-}
-
-// ------------------------------------------------------- matrix-free D, G, Gt_G ----
-// The pressure-side operators rebuilt per row from the cell thn table: D (pressure rows, reading the 4
-// velocity fields), G (velocity rows, reading pressure) and Gt_G = -(D G) (pressure rows), with the
-// arithmetic of phase_D_row / phase_G_row (x d_p) / k_spgemm_fill (products accumulated in D's column
-// order, then scaled by alpha = -1) and summed in CSR column order -- the assembled operators' results
-// bit for bit.  Needs n >= 3 (distinct periodic neighbours).
-struct PGDev {
-    static constexpr bool kFast = false;
-    int n;
-    const double* cell;
-    double d_p, inv, minv;   // d_p, 1.0 / dx, -1.0 / dx  (dx == dy; evaluated as the assembly does)
-    // partition of the INPUT vector's grid rows, as FStencilDev (one GPU: r0 = 0, L = n, h = 0)
-    int r0, L, h, which;
-    int ext = 0;   // which = 3: ghost rows computed on each side
-    int oh = 0;    // ghost depth of the output's layout (D: pressure, G: velocity, Gt_G: == h)
-    int unit = 0;  // d_p == 1 and minv == -inv: Gt_G's eight products per phase are +-X^2 (GtGStencilDev::entries)
-    __device__ int wrap(int a) const { return a < 0 ? a + n : (a >= n ? a - n : a); }
-    template <int NFI>
-    __device__ int32_t xrow_of(int f, int gr) const {
-        if (h == 0) return (f * n + wrap(gr)) * n;
-        return ext_row(NFI, f, gr - r0, L, h, n);
-    }
-    template <int NFO>
-    __device__ int32_t out_of(int f, int lr, int gc) const {
-        return (lr >= 0 && lr < L ? (f * L + lr) * n : ext_row(NFO, f, lr, L, oh, n)) + gc;
-    }
-};
-
-// y = D x: pressure row (gr, gc) = sum over phases of the 4 velocity entries in column order.
-struct DStencilDev : PGDev {
-    struct Cell {};
-    __device__ Cell cell_pre(int, int) const { return {}; }
-    static constexpr int NF = 4, NOUT = 1;
-    __device__ int32_t xrow(int f, int gr) const { return xrow_of<4>(f, gr); }
-    __device__ int32_t out_row(int, int lr, int gc) const { return out_of<1>(0, lr, gc); }
-    template <bool EDGE, class TA, class XA>
-    __device__ double row(int, int gr, int gc, const TA& ta, const XA& xa, double* dg, const Cell&) const {
-        const bool lastc = EDGE && gc == n - 1, lastr = EDGE && gr == n - 1;   // wrapped neighbour sorts first
-        double acc = 0.0;
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const double t0 = ta.T(p, gr, gc), tE = ta.T(p, gr, gc + 1), tW = ta.T(p, gr, gc - 1);
-            const double tN = ta.T(p, gr - 1, gc), tS = ta.T(p, gr + 1, gc);
-            const double uE = (inv * (0.5 * (t0 + tE))) * xa.X(2 * p, gr, gc + 1);
-            const double uC = (minv * (0.5 * (t0 + tW))) * xa.X(2 * p, gr, gc);
-            const double vC = (inv * (0.5 * (t0 + tN))) * xa.X(2 * p + 1, gr, gc);
-            const double vS = (minv * (0.5 * (t0 + tS))) * xa.X(2 * p + 1, gr + 1, gc);
-            acc += lastc ? uE : uC;
-            acc += lastc ? uC : uE;
-            acc += lastr ? vS : vC;
-            acc += lastr ? vC : vS;
-        }
-        *dg = 0.0;
-        return acc;
-    }
-};
-
-// y = G x: velocity row o (u_n, v_n, u_s, v_s) at (gr, gc), two pressure entries in column order.
-struct GStencilDev : PGDev {
-    struct Cell {};
-    __device__ Cell cell_pre(int, int) const { return {}; }
-    static constexpr int NF = 1, NOUT = 4;
-    __device__ int32_t xrow(int f, int gr) const { return xrow_of<1>(f, gr); }
-    __device__ int32_t out_row(int f, int lr, int gc) const { return out_of<4>(f, lr, gc); }
-    template <bool EDGE, class TA, class XA>
-    __device__ double row(int o, int gr, int gc, const TA& ta, const XA& xa, double* dg, const Cell&) const {
-        const int p = o >> 1;
-        const double t0 = ta.T(p, gr, gc), xC = xa.X(0, gr, gc);
-        double acc = 0.0;
-        *dg = 0.0;
-        if ((o & 1) == 0) {   // u row: entries p(gr, gc-1), p(gr, gc); the wrapped one sorts last
-            const double gu = 0.5 * (t0 + ta.T(p, gr, gc - 1));
-            const double uC = (d_p * (inv * gu)) * xC, uW = (d_p * (minv * gu)) * xa.X(0, gr, gc - 1);
-            const bool wrapw = EDGE && gc == 0;
-            acc += wrapw ? uC : uW;
-            acc += wrapw ? uW : uC;
-        } else {              // v row: entries p(gr-1, gc), p(gr, gc)
-            const double gv = 0.5 * (t0 + ta.T(p, gr - 1, gc));
-            const double vC = (d_p * (minv * gv)) * xC, vN = (d_p * (inv * gv)) * xa.X(0, gr - 1, gc);
-            const bool wrapn = EDGE && gr == 0;
-            acc += wrapn ? vC : vN;
-            acc += wrapn ? vN : vC;
-        }
-        return acc;
-    }
-};
-
-// y = A x, A = [[F, d_p G], [d_div D, 0]] (build_row's MPBP_OP_A; np.matmul(A, u_vec), apply.py:72): the five rows
-// of a cell -- u_n, v_n, u_s, v_s and pressure -- from the five staged fields [u_n | v_n | u_s | v_s | p], one
-// marching launch, nothing assembled.  FS is the F policy (FStencilDev, FStencilDevM<M>, FStencilFast) whose rows
-// the velocity rows start from.  Exact numerics reproduce the assembled row's sequential sum: a velocity row is F's
-// row sum with the two G products added to the SAME accumulator ((F-sum + g1) + g2: G's columns 4N + ... sort after
-// all of F's), in GStencilDev::row's order; the pressure row is DStencilDev::row's eight products in its order,
-// each entry d_div * (inv * avg) as the assembly forms it (phase_D_row's value scaled by d_div).  With FStencilFast
-// the velocity rows start from the regrouped rows (rows4); the G products and the pressure row are the exact ones
-// (explicit operations, the file is built without contraction), so pressure rows agree bit for bit in both modes.
-// n >= 3.  PART = false: one GPU, whole-grid layouts.  PART = true: the rank's rows of a row partition (FS's r0, L, h,
-// which = 0 / 1 / 2): x in the 5-field owned + ghost layout (ext_row), y and z the owned rows alone (A's product has
-// no ghost rows); the thn tables, cell_pre, the column wrap and the EDGE test stay in global grid coordinates, so a
-// row's operations and their order are the one-GPU instance's.
-template <class FS, bool PART = false>
-struct StokesADev : FS {
-    double d_p, d_div, inv, minv;   // inv = 1.0 / dx, minv = -1.0 / dx as phase_D_row / phase_G_row evaluate them
-    static constexpr int NF = 5, NOUT = 5;
-    __device__ int32_t xrow(int f, int gr) const {
-        if constexpr (PART) return ext_row(5, f, gr - this->r0, this->L, this->h, this->n);
-        else return (f * this->n + this->wrap(gr)) * this->n;
-    }
-    __device__ int32_t out_row(int o, int lr, int gc) const {
-        if constexpr (PART) return (o * this->L + lr) * this->n + gc;
-        else return (o * this->n + lr) * this->n + gc;
-    }
-    // velocity row o's two G products added to acc: the wrapped neighbour sorts last
-    template <bool EDGE, class TA, class XA>
-    __device__ double add_g(double acc, int o, int gr, int gc, const TA& ta, const XA& xa) const {
-        const int p = o >> 1;
-        const double t0 = ta.T(p, gr, gc), xC = xa.X(4, gr, gc);
-        if ((o & 1) == 0) {   // u row: entries p(gr, gc-1), p(gr, gc)
-            const double gu = 0.5 * (t0 + ta.T(p, gr, gc - 1));
-            const double uC = (d_p * (inv * gu)) * xC, uW = (d_p * (minv * gu)) * xa.X(4, gr, gc - 1);
-            const bool wrapw = EDGE && gc == 0;
-            acc += wrapw ? uC : uW;
-            acc += wrapw ? uW : uC;
-        } else {              // v row: entries p(gr-1, gc), p(gr, gc)
-            const double gv = 0.5 * (t0 + ta.T(p, gr - 1, gc));
-            const double vC = (d_p * (minv * gv)) * xC, vN = (d_p * (inv * gv)) * xa.X(4, gr - 1, gc);
-            const bool wrapn = EDGE && gr == 0;
-            acc += wrapn ? vC : vN;
-            acc += wrapn ? vN : vC;
-        }
-        return acc;
-    }
-    // pressure row: phase n then phase s, the wrapped neighbour first
-    template <bool EDGE, class TA, class XA>
-    __device__ double p_row(int gr, int gc, const TA& ta, const XA& xa) const {
-        const int n = this->n;
-        const bool lastc = EDGE && gc == n - 1, lastr = EDGE && gr == n - 1;
-        double acc = 0.0;
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const double t0 = ta.T(p, gr, gc), tE = ta.T(p, gr, gc + 1), tW = ta.T(p, gr, gc - 1);
-            const double tN = ta.T(p, gr - 1, gc), tS = ta.T(p, gr + 1, gc);
-            const double uE = (d_div * (inv * (0.5 * (t0 + tE)))) * xa.X(2 * p, gr, gc + 1);
-            const double uC = (d_div * (minv * (0.5 * (t0 + tW)))) * xa.X(2 * p, gr, gc);
-            const double vC = (d_div * (inv * (0.5 * (t0 + tN)))) * xa.X(2 * p + 1, gr, gc);
-            const double vS = (d_div * (minv * (0.5 * (t0 + tS)))) * xa.X(2 * p + 1, gr + 1, gc);
-            acc += lastc ? uE : uC;
-            acc += lastc ? uC : uE;
-            acc += lastr ? vS : vC;
-            acc += lastr ? vC : vS;
-        }
-        return acc;
-    }
-    template <bool EDGE, class TA, class XA>
-    __device__ double row(int o, int gr, int gc, const TA& ta, const XA& xa, double* dg,
-                          const typename FS::Cell& cl) const {
-        if (o == 4) {
-            *dg = 0.0;
-            return p_row<EDGE>(gr, gc, ta, xa);
-        }
-        return add_g<EDGE>(FS::template row<EDGE>(o, gr, gc, ta, xa, dg, cl), o, gr, gc, ta, xa);
-    }
-    // tolerance mode (FS = FStencilFast): the five rows at once; no diagonal is handed over (rd unused by the
-    // store / add / residual epilogues)
-    template <class TA, class XA>
-    __device__ void rows4(int gr, int gc, const TA& ta, const XA& xa, const typename FS::Cell& cl, double* acc,
-                          double* rd) const {
-        FS::template rows4<false>(gr, gc, ta, xa, cl, acc, rd);
-#pragma unroll
-        for (int o = 0; o < 4; ++o) acc[o] = add_g<true>(acc[o], o, gr, gc, ta, xa);
-        acc[4] = p_row<true>(gr, gc, ta, xa);
-#pragma unroll
-        for (int o = 0; o < 5; ++o) rd[o] = 0.0;
-    }
-};
-
-template <bool PART, class Epi>
-int launch_stokes_a(const FStencilDev& P, double d_p, double d_div, const double* x, Epi epi, hipStream_t st,
-                    bool fast) {
-    const double dx = 1.0 / P.n;
-    auto go = [&](const auto& Q) {
-        using S = StokesADev<std::decay_t<decltype(Q)>, PART>;
-        const S A{Q, d_p, d_div, 1.0 / dx, -1.0 / dx};
-        const int64_t chunks = march_chunks(A, KO().march_rows, march_capacity<k_march<S, XPlain, Epi, BNone>>());
-        if (chunks == 0) return (int)MPBP_OK;
-        const int64_t strips = (A.n + kMB - 1) / kMB;
-        k_march<S, XPlain, Epi, BNone><<<(unsigned)(chunks * strips), kMB, 0, st>>>(A, XPlain{x}, (int)chunks, epi, BNone{});
-        MPBP_HIP(hipGetLastError());
-        return (int)MPBP_OK;
-    };
-    if constexpr (std::is_same_v<Epi, EpiStore>) return with_f_policy(P, fast, go);
-    // ADD / RESID: the M = 13 and M = 5 identity instances spilled (8 / 24 B per lane) beside the z operand; these
-    // modes take the general exact rows there (the same bits: the identities only skip exactly known multiplies)
-    if (fast) return go(FStencilFast{P});
-    if (P.d_u == -1.0 && P.eta_s == 1.0 && P.eta_n == 1.0) return go(FStencilDevM<7>{P});
-    return go(P);
-}
-
-// Gt_G = -(D G): row (gr, gc) has the five entries N, W, C, E, S (grid neighbours).  Each off-diagonal
-// gets one product per phase; the diagonal gets four per phase, accumulated in D's column order.
-struct GtGStencilDev : PGDev {
-    struct Cell {};
-    __device__ Cell cell_pre(int, int) const { return {}; }
-    static constexpr int NF = 1, NOUT = 1;
-    __device__ int32_t xrow(int f, int gr) const { return xrow_of<1>(f, gr); }
-    __device__ int32_t out_row(int, int lr, int gc) const { return out_of<1>(0, lr, gc); }
-    // e = {N, W, C, E, S}.  (vr, vc): the cell in the accessor's coordinates (it may lie up to a few cells
-    // outside the grid in the fused solve); (gr, gc): the same cell wrapped onto the grid.
-    template <class TA>
-    __device__ void entries(int vr, int vc, int gr, int gc, const TA& ta, double* e) const {
-        const bool lastc = gc == n - 1, lastr = gr == n - 1;
-        double cN = 0.0, cW = 0.0, cC = 0.0, cE = 0.0, cS = 0.0;
-        if (unit) {
-            // d_p == 1 and minv == -inv: with X = inv * (0.5 * (t0 + t_nb)) per face, every D entry is +-X and
-            // every G factor d_p * (+-inv * g) is +-X too (g is the same half sum), so the eight products below
-            // are +-X^2 -- the same roundings (RN(-a b) = -RN(a b)), same bits, 12 multiplies per phase, not 28
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const double t0 = ta.T(p, vr, vc), tE = ta.T(p, vr, vc + 1), tW = ta.T(p, vr, vc - 1);
-                const double tN = ta.T(p, vr - 1, vc), tS = ta.T(p, vr + 1, vc);
-                const double XW = inv * (0.5 * (t0 + tW)), XE = inv * (0.5 * (t0 + tE));
-                const double XN = inv * (0.5 * (t0 + tN)), XS = inv * (0.5 * (t0 + tS));
-                const double qW = XW * XW, qE = XE * XE, qN = XN * XN, qS = XS * XS;
-                // uC_C = -qW, uC_W = qW, uE_E = qE, uE_C = -qE, vC_C = -qN, vC_N = qN, vS_S = qS, vS_C = -qS
-                const double u1 = lastc ? -qE : -qW, u2 = lastc ? -qW : -qE;
-                const double v1 = lastr ? -qS : -qN, v2 = lastr ? -qN : -qS;
-                if (p == 0) {
-                    cC = u1; cW = qW; cE = qE; cN = qN; cS = qS;
-                } else {
-                    cC += u1; cW += qW; cE += qE; cN += qN; cS += qS;
-                }
-                cC += u2;
-                cC += v1;
-                cC += v2;
-            }
-            e[0] = -1.0 * cN; e[1] = -1.0 * cW; e[2] = -1.0 * cC; e[3] = -1.0 * cE; e[4] = -1.0 * cS;
-            return;
-        }
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const double t0 = ta.T(p, vr, vc), tE = ta.T(p, vr, vc + 1), tW = ta.T(p, vr, vc - 1);
-            const double tN = ta.T(p, vr - 1, vc), tS = ta.T(p, vr + 1, vc);
-            // D row entries (phase_D_row)
-            const double DuE = inv * (0.5 * (t0 + tE)), DuC = minv * (0.5 * (t0 + tW));
-            const double DvC = inv * (0.5 * (t0 + tN)), DvS = minv * (0.5 * (t0 + tS));
-            // G rows of the velocity unknowns u(gr,gc), u(gr,gc+1), v(gr,gc), v(gr+1,gc) (phase_G_row x d_p)
-            const double gC = 0.5 * (t0 + tW), gE = 0.5 * (tE + t0);
-            const double gN = 0.5 * (t0 + tN), gS = 0.5 * (tS + t0);
-            const double uC_C = DuC * (d_p * (inv * gC)), uC_W = DuC * (d_p * (minv * gC));
-            const double uE_E = DuE * (d_p * (inv * gE)), uE_C = DuE * (d_p * (minv * gE));
-            const double vC_C = DvC * (d_p * (minv * gN)), vC_N = DvC * (d_p * (inv * gN));
-            const double vS_S = DvS * (d_p * (minv * gS)), vS_C = DvS * (d_p * (inv * gS));
-            const double u1 = lastc ? uE_C : uC_C, u2 = lastc ? uC_C : uE_C;
-            const double v1 = lastr ? vS_C : vC_C, v2 = lastr ? vC_C : vS_C;
-            if (p == 0) {   // first touch stores the product itself (k_spgemm_fill)
-                cC = u1; cW = uC_W; cE = uE_E; cN = vC_N; cS = vS_S;
-            } else {
-                cC += u1; cW += uC_W; cE += uE_E; cN += vC_N; cS += vS_S;
-            }
-            cC += u2;
-            cC += v1;
-            cC += v2;
-        }
-        e[0] = -1.0 * cN; e[1] = -1.0 * cW; e[2] = -1.0 * cC; e[3] = -1.0 * cE; e[4] = -1.0 * cS;
-    }
-    // Gt_G x at a cell: the five entries summed in CSR column order (EDGE: sorted by wrapped column)
-    template <bool EDGE, class TA, class XA>
-    __device__ double apply_v(int vr, int vc, int gr, int gc, const TA& ta, const XA& xa, double* dg) const {
-        double e[5];
-        entries(vr, vc, gr, gc, ta, e);
-        *dg = e[2];
-        const double p[5] = {e[0] * xa.X(0, vr - 1, vc), e[1] * xa.X(0, vr, vc - 1), e[2] * xa.X(0, vr, vc),
-                             e[3] * xa.X(0, vr, vc + 1), e[4] * xa.X(0, vr + 1, vc)};
-        return add5<EDGE>(0.0, p, Wrap{gr == 0, gr == n - 1, gc == 0, gc == n - 1});
-    }
-    template <bool EDGE, class TA, class XA>
-    __device__ double row(int, int gr, int gc, const TA& ta, const XA& xa, double* dg, const Cell&) const {
-        return apply_v<EDGE>(gr, gc, gr, gc, ta, xa, dg);
-    }
-};
-
-// ---- one Gt_G Chebyshev solve in one launch (k_gtg_solve) ----
-// The pressure solves x = Gt_G^-1 b of the apply (solve.py:265, 271) as K Chebyshev-Jacobi sweeps from x0 = 0, fused:
-// a workgroup owns a TW x TH tile of cells and stages b and thn over the tile plus a halo of H = K - 1 cells, and
-// x0 = d0 = c2_0 (b / diag) there from the stored diagonal (level 0).  Level l = 1 .. H recomputes the tile with halo
-// H - l from level l - 1 (LDS ping-pong), the last writing the tile.  As in k_fsolve every cell has one owning lane for
-// all its levels (the lane's two tile cells, and cell t of each halo ring r = 1 .. H - 1), which builds the cell's five
-// entries once (GtGStencilDev::entries, from the staged thn) and keeps them, b and d in registers: a level reads only
-// the five x values of the stencil from LDS.  Each row is GtGStencilDev::apply_v's IEEE operations (the entries', the
-// products', add5's column order) and each update the Chebyshev epilogue's (EpiChebFirst at level 1, EpiCheb after):
-// bit-identical to the K - 1 sweeps of the per-sweep path, for one launch and one pass over b instead of K - 1 passes
-// over x, d, b.
-constexpr int kGTW = kFTW, kGTH = kFTH;   // the 64 x 8 tile and ring numbering of k_fsolve (fs_ring_cell)
-struct ChebK {
-    double c1[8], c2[8];   // sweep s's coefficients (c2[0]: the initial iterate's)
-};
-template <int H, int GW = kGTW, int GH = kGTH>
-struct GtgTile {   // a GW x GH tile of cells with H halo levels
-    static constexpr int RW = GW + 2 * H, RH = GH + 2 * H, N = RW * RH;
-    static constexpr int ring(int r) { return 2 * GW + 2 * GH - 4 + 8 * r; }   // cells of halo ring r
-    static constexpr int rings(int h) { return h < 1 ? 0 : ring(h) + rings(h - 1); }
-};
-template <int H>
-struct TTile {   // thn of the staged tile; (r, c) in the tile's virtual grid coordinates
-    const double* t;
-    int rb, cb;
-    __device__ double T(int sph, int r, int c) const {
-        const double v = t[(r - rb) * GtgTile<H>::RW + (c - cb)];
-        return sph ? 1.0 - v : v;
-    }
-};
-
-// PART: the tiles cover a row partition's owned rows and P.ext ghost rows each side (the CA schedule); b and diag in
-// its ghost layout (depth P.h >= P.ext + H; deeper rows, read only for cells no output depends on, clamped), out in
-// the output layout (depth P.oh).
-// TPB = 512: one tile cell and at most one ring cell per lane (rings 1 .. H - 1 numbered across the workgroup), so a
-// level's critical path is half as long and the smaller register state lets more waves share the CU.
-// DB (one GPU): the right-hand side is rhs = D Y + v_p (solve.py:259), built at every staged cell with
-// DStencilDev::row's operations and EpiAdd's sum from thn staged one cell wider and Y (the four velocity fields) from
-// memory: the D launch, and rhs's write and re-read, disappear.
-struct GtgD {
-    const double* Y;    // Finv_v: u_n, v_n, u_s, v_s
-    const double* vp;   // v's pressure part
-};
-template <int H, bool PART, int TPB, bool DB, int GW = kGTW, int GH = kGTH>
-__global__ void __launch_bounds__(TPB) MPBP_LDS_READS k_gtg_solve(GtGStencilDev P, const double* __restrict__ b,
-                                                   const double* __restrict__ diag, ChebK ck, double* __restrict__ out,
-                                                   GtgD dv) {
-    using G = GtgTile<H, GW, GH>;
-    constexpr int SW = DB ? G::RW + 2 : G::RW, TN = DB ? SW * (G::RH + 2) : G::N;   // staged thn
-    constexpr int NM = GW * GH / TPB;                // tile cells per lane
-    constexpr int NR = TPB == 256 ? H - 1 : 1;       // ring slots per lane (rings 1 .. H - 1)
-    constexpr int NS = NM + NR;
-    static_assert(NM * TPB == GW * GH && TPB % GW == 0, "whole tile rows per lane group");
-    static_assert(TPB == 512 || G::ring(H - 1) <= 256, "256 lanes own one cell of each ring");
-    static_assert(TPB == 256 || G::rings(H - 1) <= 512, "512 lanes own at most one ring cell each");
-    __shared__ double ts[TN], bs[G::N], xa[G::N], xb[G::N];
-    const int n = P.n;
-    const int tx = (n + GW - 1) / GW;
-    const int bk = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int lo = PART ? P.r0 - P.ext : 0, hi = PART ? P.r0 + P.L + P.ext : n;   // output rows [lo, hi)
-    const int r0 = lo + (bk / tx) * GH, c0 = (bk % tx) * GW;
-    const int rb = r0 - H, cb = c0 - H;   // virtual coordinates of staged cell 0
-    const int tid = threadIdx.x;
-    // level 0 over the whole staged region: thn, b, x0 = c2_0 (b / diag); every load issued before the first LDS store
-    if constexpr (DB) {
-        const int nn = n * n;
-        {   // thn one cell wider than the staged region
-            constexpr int IT = (TN + TPB - 1) / TPB;
-            double tv[IT];
-#pragma unroll
-            for (int it = 0; it < IT; ++it) {
-                const int i = tid + it * TPB;
-                if (i < TN) {
-                    const int rr = i / SW, cc = i - rr * SW;
-                    tv[it] = P.cell[P.wrap(rb - 1 + rr) * n + P.wrap(cb - 1 + cc)];
-                }
-            }
-#pragma unroll
-            for (int it = 0; it < IT; ++it)
-                if (tid + it * TPB < TN) ts[tid + it * TPB] = tv[it];
-        }
-        // every staged cell's Y, v_p and diagonal loaded ahead of the barrier: one memory latency, not one per cell
-        constexpr int IY = (G::N + TPB - 1) / TPB;
-        double yl[IY][8], vpl[IY], dgl[IY];
-#pragma unroll
-        for (int it = 0; it < IY; ++it) {
-            const int i = tid + it * TPB;
-            if (i >= G::N) break;
-            const int rr = i / G::RW, cc = i - rr * G::RW;
-            const int gr = P.wrap(rb + rr), gc = P.wrap(cb + cc);
-            const int ge = gc == n - 1 ? 0 : gc + 1, gs = gr == n - 1 ? 0 : gr + 1;
-            const int32_t k = gr * n + gc;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                yl[it][4 * q + 0] = dv.Y[2 * q * nn + gr * n + ge];         // u at the east face
-                yl[it][4 * q + 1] = dv.Y[2 * q * nn + k];                   // u at the cell's west face
-                yl[it][4 * q + 2] = dv.Y[(2 * q + 1) * nn + k];             // v at its north face
-                yl[it][4 * q + 3] = dv.Y[(2 * q + 1) * nn + gs * n + gc];   // v at the south face
-            }
-            vpl[it] = dv.vp[k];
-            dgl[it] = diag[k];
-        }
-        __syncthreads();
-        const TTileT<SW> tD{ts, rb - 1, cb - 1};
-#pragma unroll
-        for (int it = 0; it < IY; ++it) {
-            const int i = tid + it * TPB;
-            if (i >= G::N) break;
-            const int rr = i / G::RW, cc = i - rr * G::RW;
-            const int vr = rb + rr, vc = cb + cc, gr = P.wrap(vr), gc = P.wrap(vc);
-            const double* yv = yl[it];
-            const double vpk = vpl[it], dgk = dgl[it];
-            const bool lastc = gc == n - 1, lastr = gr == n - 1;   // the wrapped neighbour sorts first (DStencilDev)
-            double acc = 0.0;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const double t0 = tD.T(q, vr, vc), tE = tD.T(q, vr, vc + 1), tWv = tD.T(q, vr, vc - 1);
-                const double tN = tD.T(q, vr - 1, vc), tS = tD.T(q, vr + 1, vc);
-                const double uE = (P.inv * (0.5 * (t0 + tE))) * yv[4 * q + 0];
-                const double uC = (P.minv * (0.5 * (t0 + tWv))) * yv[4 * q + 1];
-                const double vC = (P.inv * (0.5 * (t0 + tN))) * yv[4 * q + 2];
-                const double vS = (P.minv * (0.5 * (t0 + tS))) * yv[4 * q + 3];
-                acc += lastc ? uE : uC;
-                acc += lastc ? uC : uE;
-                acc += lastr ? vS : vC;
-                acc += lastr ? vC : vS;
-            }
-            const double bvv = acc + vpk;   // EpiAdd
-            bs[i] = bvv;
-            xa[i] = ck.c2[0] * (bvv / dgk);
-        }
-    } else {
-        constexpr int IT = (G::N + TPB - 1) / TPB;
-        double bv[IT], tv[IT], dv_[IT];
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * TPB;
-            if (i < G::N) {
-                const int rr = i / G::RW, cc = i - rr * G::RW;
-                const int gr = P.wrap(rb + rr), gc = P.wrap(cb + cc);
-                int32_t kb = gr * n + gc;
-                if constexpr (PART) {
-                    int lr = rb + rr - P.r0;
-                    lr = lr < -P.h ? -P.h : (lr >= P.L + P.h ? P.L + P.h - 1 : lr);
-                    kb = ext_row(1, 0, lr, P.L, P.h, n) + gc;
-                }
-                bv[it] = b[kb];
-                tv[it] = P.cell[gr * n + gc];
-                dv_[it] = diag[kb];
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * TPB;
-            if (i < G::N) {
-                ts[i] = tv[it];
-                bs[i] = bv[it];
-                xa[i] = ck.c2[0] * (bv[it] / dv_[it]);
-            }
-        }
-    }
-    __syncthreads();
-    // the owned cells (slot 0, 1: the tile's; slot 1 + r: ring r), their entries, b and d0 = x0
-    const TTileT<SW> ta{ts, DB ? rb - 1 : rb, DB ? cb - 1 : cb};
-    const int lr = tid / GW, lc = tid % GW;
-    int cr[NS], cc[NS], si[NS], rr[NS];
-    bool own[NS], edge[NS];
-    double e[NS][5], bo[NS], d[NS];
-#pragma unroll
-    for (int m = 0; m < NM; ++m) {
-        cr[m] = r0 + lr + (TPB / GW) * m; cc[m] = c0 + lc; own[m] = true; rr[m] = 0;
-    }
-    if constexpr (TPB == 256) {
-#pragma unroll
-        for (int r = 1; r < H; ++r) {
-            own[NM + r - 1] = tid < G::ring(r);
-            rr[NM + r - 1] = r;
-            fs_ring_cell_t<GW, GH>(r, own[NM + r - 1] ? tid : 0, r0, c0, cr[NM + r - 1], cc[NM + r - 1]);
-        }
-    } else if constexpr (NR > 0) {
-        int r = 0, j = tid;   // rings 1 .. H - 1 numbered ring 1 first: lane t owns cell t of that sequence
-#pragma unroll
-        for (int q = 1; q < H; ++q)
-            if (r == 0) {
-                if (j < G::ring(q)) r = q;
-                else j -= G::ring(q);
-            }
-        own[NM] = r != 0;
-        rr[NM] = r;
-        fs_ring_cell_t<GW, GH>(r ? r : 1, r ? j : 0, r0, c0, cr[NM], cc[NM]);
-    }
-#pragma unroll
-    for (int sl = 0; sl < NS; ++sl) {
-        const int vr = cr[sl], vc = cc[sl], gr = P.wrap(vr), gc = P.wrap(vc);
-        si[sl] = (vr - rb) * G::RW + (vc - cb);
-        edge[sl] = __builtin_amdgcn_readfirstlane(__any(own[sl] && (gr == 0 || gr == n - 1 || gc == 0 ||
-                                                                    gc == n - 1))) != 0;
-        if (own[sl]) {
-            P.entries(vr, vc, gr, gc, ta, e[sl]);
-            bo[sl] = bs[si[sl]];
-            d[sl] = xa[si[sl]];
-        }
-    }
-    double* cur = xa;
-    double* nxt = xb;
-#pragma unroll
-    for (int l = 1; l <= H; ++l) {
-        if (l > 1) __syncthreads();
-        const double c1 = ck.c1[l], c2 = ck.c2[l];
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) {
-            if (TPB == 256 && sl >= NM && sl - NM + 1 > H - l) continue;   // (compile time) ring sl - NM + 1 is done
-            if (sl >= NM && (!own[sl] || rr[sl] > H - l)) continue;        // ring rr lives through level H - rr
-            const int vr = cr[sl], vc = cc[sl];
-            if (l == H && (vr >= hi || vc >= n)) continue;            // a tile past the last row / column
-            const int i = si[sl];
-            const double p[5] = {e[sl][0] * cur[i - G::RW], e[sl][1] * cur[i - 1], e[sl][2] * cur[i],
-                                 e[sl][3] * cur[i + 1], e[sl][4] * cur[i + G::RW]};
-            const int gr = P.wrap(vr), gc = P.wrap(vc);
-            const Wrap wr{gr == 0, gr == n - 1, gc == 0, gc == n - 1};
-            const double acc = edge[sl] ? add5<true>(0.0, p, wr) : add5<false>(0.0, p, wr);
-            const double z = (bo[sl] - acc) / e[sl][2];
-            const double dn = c1 * d[sl] + c2 * z;
-            const double x = cur[i] + dn;
-            if (l < H) {
-                nxt[i] = x;
-                d[sl] = dn;
-            } else {
-                out[PART ? P.out_row(0, vr - P.r0, vc) : vr * n + vc] = x;
-            }
-        }
-        double* t = cur;
-        cur = nxt;
-        nxt = t;
-    }
-}
-
-
-// ---- multigrid level 0 of the pressure hierarchy (matrix-free Gt_G): descent and ascent in one launch each ----
-// k_gpre: x0 = c2_0 (b / diag) over the tile + 3, the Chebyshev sweep x1 over the tile + 2 (written on the tile), the
-// residual r = b - Gt_G x1 over the tile + 1 (in LDS) and R_0 r on the tile's 32 x 4 coarse cells (cell-centred both
-// ways).  k_gpost: x = x_in + P_0 x_c staged over the tile + 2, two Chebyshev sweeps from d = +0.0 (the restart of the
-// post-smoothing), the last writing the tile (sub - x when sub is set).  k_gtg_solve's 512-lane layout (one tile cell
-// and at most one ring cell per lane, the cell's five entries built once from thn), its rows and updates, the
-// transfers' k_mg_transfer_spmv lists and orders, EpiResid's and EpiAdd's sums: bit-identical to the launches they
-// replace (the first / plain / zero-direction sweeps, the residual, the restriction, the prolongation).
-template <int KY, int KX, int W>
-__device__ inline double g1_rw(const double* tf, int cr, int cc, int n, int rb, int cb);
-template <bool PRE, bool SUB>
-__global__ void __launch_bounds__(512) MPBP_LDS_READS
-k_gtg_level0(GtGStencilDev P, const double* __restrict__ b, const double* __restrict__ diag, const double* __restrict__ xin,
-             const double* __restrict__ xc, const double* __restrict__ sub, ChebK ck, double* __restrict__ x_out,
-             double* __restrict__ bc) {
-    constexpr int H = PRE ? 3 : 2;   // staged halo: the tile + H
-    using G = GtgTile<H>;
-    constexpr int CW = kGTW / 2 + 4, CH = kGTH / 2 + 4, CN = CW * CH;   // k_gpost's coarse window (k_gal1's geometry)
-    static_assert(CW == kG1CW, "g1_p_in's window stride");
-    __shared__ double ts[G::N], bs[G::N], xa[G::N], xb[G::N];
-    __shared__ double cs[PRE ? 1 : CN];
-    const int n = P.n, nc = n >> 1;
-    const int tx = (n + kGTW - 1) / kGTW;
-    const int bk = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int r0 = (bk / tx) * kGTH, c0 = (bk % tx) * kGTW;
-    const int rb = r0 - H, cb = c0 - H;
-    const int cr0 = r0 >> 1, cc0 = c0 >> 1;
-    const int tid = threadIdx.x;
-    auto wrapc = [&](int q) { return q < 0 ? q + nc : (q >= nc ? q - nc : q); };
-    {
-        constexpr int IT = (G::N + 511) / 512, IC = PRE ? 1 : (CN + 511) / 512;
-        double bv[IT], tv[IT], wv[IT], cv[IC];
-        if constexpr (!PRE) {
-#pragma unroll
-            for (int it = 0; it < IC; ++it) {
-                const int i = tid + it * 512;
-                if (i < CN) {
-                    const int r = i / CW, c = i - r * CW;
-                    cv[it] = xc[wrapc(cr0 - 2 + r) * nc + wrapc(cc0 - 2 + c)];
-                }
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 512;
-            if (i < G::N) {
-                const int rr = i / G::RW, cc = i - rr * G::RW;
-                const int32_t k = P.wrap(rb + rr) * n + P.wrap(cb + cc);
-                bv[it] = b[k];
-                tv[it] = P.cell[k];
-                wv[it] = PRE ? diag[k] : xin[k];
-            }
-        }
-        if constexpr (!PRE) {
-#pragma unroll
-            for (int it = 0; it < IC; ++it)
-                if (tid + it * 512 < CN) cs[tid + it * 512] = cv[it];
-            __syncthreads();
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 512;
-            if (i < G::N) {
-                ts[i] = tv[it];
-                bs[i] = bv[it];
-                if constexpr (PRE) {
-                    xa[i] = ck.c2[0] * (bv[it] / wv[it]);   // x0 (k_cheb_init's expression, XInit's)
-                } else {                                     // x_in + P_0 x_c (the prolongation's sum)
-                    const int rr = i / G::RW, cc = i - rr * G::RW;
-                    const double pc = g1_inner(cr0, cc0, kGTH / 2, kGTW / 2, nc)
-                                          ? g1_p_in<MPBP_MG_CELL, MPBP_MG_CELL>(cs, rr, cc)
-                                          : g1_p<MPBP_MG_CELL, MPBP_MG_CELL>(cs, P.wrap(rb + rr), P.wrap(cb + cc), nc,
-                                                                             cr0 - 2, cc0 - 2);
-                    xa[i] = pc + wv[it];
-                }
-            }
-        }
-    }
-    __syncthreads();
-    const TTileT<G::RW> ta{ts, rb, cb};
-    const int lr = tid >> 6, lc = tid & 63;
-    // slot 0: the tile cell; slot 1: ring cell t of rings 1 .. H - 1 numbered ring 1 first
-    int cr[2], cc[2], si[2], rr[2];
-    bool own[2], edge[2];
-    double e[2][5], bo[2], d[2];
-    cr[0] = r0 + lr; cc[0] = c0 + lc; own[0] = true; rr[0] = 0;
-    {
-        int r = 0, j = tid;
-#pragma unroll
-        for (int q = 1; q < H; ++q)
-            if (r == 0) {
-                if (j < 140 + 8 * q) r = q;
-                else j -= 140 + 8 * q;
-            }
-        own[1] = r != 0;
-        rr[1] = r;
-        fs_ring_cell(r ? r : 1, r ? j : 0, r0, c0, cr[1], cc[1]);
-    }
-#pragma unroll
-    for (int sl = 0; sl < 2; ++sl) {
-        const int vr = cr[sl], vc = cc[sl], gr = P.wrap(vr), gc = P.wrap(vc);
-        si[sl] = (vr - rb) * G::RW + (vc - cb);
-        edge[sl] = __builtin_amdgcn_readfirstlane(__any(own[sl] && (gr == 0 || gr == n - 1 || gc == 0 ||
-                                                                    gc == n - 1))) != 0;
-        if (own[sl]) {
-            P.entries(vr, vc, gr, gc, ta, e[sl]);
-            bo[sl] = bs[si[sl]];
-            d[sl] = PRE ? xa[si[sl]] : 0.0;   // PRE: d0 = x0; post: the restart's +0.0
-        }
-    }
-    double* cur = xa;
-    double* nxt = xb;
-    constexpr int L = PRE ? 2 : 2;   // PRE: the sweep, then the residual; post: two sweeps
-#pragma unroll
-    for (int l = 1; l <= L; ++l) {
-        if (l > 1) __syncthreads();
-        const double c1 = ck.c1[l], c2 = ck.c2[l];
-#pragma unroll
-        for (int sl = 0; sl < 2; ++sl) {
-            // PRE: ring rr lives through level 3 - rr (the residual at level 2 covers the tile + 1); post: 2 - rr
-            if (sl == 1 && (!own[1] || rr[1] > (PRE ? 3 : 2) - l)) continue;
-            const int vr = cr[sl], vc = cc[sl];
-            const int i = si[sl];
-            const double p[5] = {e[sl][0] * cur[i - G::RW], e[sl][1] * cur[i - 1], e[sl][2] * cur[i],
-                                 e[sl][3] * cur[i + 1], e[sl][4] * cur[i + G::RW]};
-            const int gr = P.wrap(vr), gc = P.wrap(vc);
-            const Wrap wr{gr == 0, gr == n - 1, gc == 0, gc == n - 1};
-            const double acc = edge[sl] ? add5<true>(0.0, p, wr) : add5<false>(0.0, p, wr);
-            if (PRE && l == 2) {   // the residual (EpiResid)
-                nxt[i] = bo[sl] - acc;
-                continue;
-            }
-            const double z = (bo[sl] - acc) / e[sl][2];
-            const double dn = c1 * d[sl] + c2 * z;
-            const double x = cur[i] + dn;
-            nxt[i] = x;
-            d[sl] = dn;
-            const bool out = PRE ? (l == 1) : (l == L);
-            if (sl == 0 && out && vr < n && vc < n) {
-                const int32_t o = vr * n + vc;
-                x_out[o] = (SUB && !PRE) ? sub[o] - x : x;
-            }
-        }
-        double* t = cur;
-        cur = nxt;
-        nxt = t;
-    }
-    if constexpr (PRE) {   // R_0 r on the tile's coarse cells (cur holds r over the tile + 1)
-        __syncthreads();
-        constexpr int CTW = kGTW / 2, CTH = kGTH / 2;   // the tile's coarse cells
-        if (tid < CTW * CTH) {
-            const int crr = cr0 + tid / CTW, ccc = cc0 + tid % CTW;
-            if (crr < nc && ccc < nc)
-                bc[crr * nc + ccc] = g1_inner(cr0, cc0, CTH, CTW, nc)
-                                         ? g1_rw_in<MPBP_MG_CELL, MPBP_MG_CELL, G::RW, 2>(cur, crr - cr0, ccc - cc0)
-                                         : g1_rw<MPBP_MG_CELL, MPBP_MG_CELL, G::RW>(cur, crr, ccc, n, rb, cb);
-        }
-    }
-}
-
-// ---- multigrid level 1 of a tolerance-mode F hierarchy in one launch (k_gal1) ----
-// A_1 x = R_0 (F (P_0 x)) (MgGal) with the two fine-size intermediates kept in LDS: a workgroup owns a 16 x 8 tile of
-// coarse cells (a 32 x 16 fine block; kGF* below), stages the coarse x of its four fields over the tile + 2 and thn
-// over the fine block + 2, builds t0 = P_0 x on the fine block + 2 (36 x 20), t1 = F t0 on the fine block + 1 (34 x 18,
-// the tolerance-mode rows), and R_0 t1 on its coarse rows, handing each to the level's epilogue.  Each value is built
-// by the operations of the three launches it replaces (k_mg_transfer_spmv's 1D lists and product order,
-// FStencilFast::rows4), so the result is bit-identical; HBM: x, thn and the epilogue operands once, no fine vector
-// written or read.  (The 32 x 4 tile of kG1* above -- the level-0 fused kernels' coarse windows -- took 42 KB of LDS,
-// three workgroups per CU: 33.1 vs 28.5 us per launch, profiles/r06s_ab_gal1_tile.txt.)
-// a grid index to its slot in a staged window starting at virtual index `base` (the window is < the grid)
-__device__ inline int g1_slot(int i, int base, int m) { int l = i - base; return l < 0 ? l + m : (l >= m ? l - m : l); }
-// P_0's row at fine (gr, gc) of a field with compile-time kinds: k_mg_transfer_spmv's list order and products
-// (S: the coarse window's row stride)
-template <int KY, int KX, int S>
-__device__ inline double g1_p(const double* xf, int gr, int gc, int nc, int rb, int cb) {
-    int yi[2], xi[2];
-    double yw[2], xw[2];
-    const int my = mg_p1d_fast(KY, nc, gr, yi, yw), mx = mg_p1d_fast(KX, nc, gc, xi, xw);
-    double acc = 0.0;
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        if (a >= my) break;
-        const double* xr = xf + g1_slot(yi[a], rb, nc) * S;
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            if (b >= mx) break;
-            acc += (yw[a] * xw[b]) * xr[g1_slot(xi[b], cb, nc)];
-        }
-    }
-    return acc;
-}
-// R_0's row at coarse (cr, cc): 4 (cell) x 3 or 4 entries, compile-time counts (S: the fine window's row stride)
-template <int KY, int KX, int S = kG1FW>
-__device__ inline double g1_r(const double* tf, int cr, int cc, int n, int rb, int cb) {
-    constexpr int MY = KY == MPBP_MG_CELL ? 4 : 3, MX = KX == MPBP_MG_CELL ? 4 : 3;
-    int yi[4], xi[4];
-    double yw[4], xw[4];
-    mg_r1d_fast(KY, n, cr, yi, yw);
-    mg_r1d_fast(KX, n, cc, xi, xw);
-    double acc = 0.0;
-#pragma unroll
-    for (int a = 0; a < MY; ++a) {
-        const double* tr1 = tf + g1_slot(yi[a], rb, n) * S;
-#pragma unroll
-        for (int b = 0; b < MX; ++b) acc += (yw[a] * xw[b]) * tr1[g1_slot(xi[b], cb, n)];
-    }
-    return acc;
-}
-// Interior tiles (no staged window wraps and no 1D list takes its periodic special case): P_0's and R_0's rows in
-// window coordinates straight from the fine / coarse parity -- the same entries, weights, order and products as
-// mg_p1d_fast / mg_r1d_fast give there, without their wrap tests, sorted-order selects and runtime weights.  A node
-// kind's one-entry row (even fine index) takes a second entry of weight 0: its products are +-0 added to a sum that
-// started from +0.0 (never -0.0), so the sum's bits are unchanged for finite x.  With t1 in t0's LDS (occupancy 2 -> 3
-// workgroups per CU): k_gal1 45 -> 33 us, multigrid apply 1.610 -> 1.510 ms (A/B on one box, profiles/r05zd_ab.txt).
-template <int K>
-__device__ inline void g1_p1d_in(int r, int& lo, double& w0, double& w1) {
-    const bool odd = r & 1;
-    if constexpr (K == MPBP_MG_CELL) {   // even: c_{i-1} (1/4), c_i (3/4); odd: c_i (3/4), c_{i+1} (1/4)
-        lo = (r >> 1) + (odd ? 1 : 0);
-        w0 = odd ? 0.75 : 0.25;
-        w1 = odd ? 0.25 : 0.75;
-    } else {                             // even: c_i (1); odd: c_i, c_{i+1} (1/2 each)
-        lo = (r >> 1) + 1;
-        w0 = odd ? 0.5 : 1.0;
-        w1 = odd ? 0.5 : 0.0;
-    }
-}
-// P_0's row at window fine (r, c) of the block + 2 (the coarse window starts two coarse cells before the tile)
-template <int KY, int KX, int S>
-__device__ inline double g1_p_in(const double* xf, int r, int c) {
-    int ry, cx;
-    double y0, y1, x0, x1;
-    g1_p1d_in<KY>(r, ry, y0, y1);
-    g1_p1d_in<KX>(c, cx, x0, x1);
-    const double* q = xf + ry * S + cx;
-    double acc = 0.0;
-    acc += (y0 * x0) * q[0];
-    acc += (y0 * x1) * q[1];
-    acc += (y1 * x0) * q[S];
-    acc += (y1 * x1) * q[S + 1];
-    return acc;
-}
-// R_0's row at tile coarse (lr, lc) over a fine window of row stride W whose slot OFF holds fine index 2 c0 - 1 (the
-// tile's first coarse cell's first restriction entry): 2 lr + OFF + 0 .. 3 (cell) / 0 .. 2 (node)
-template <int KY, int KX, int W, int OFF>
-__device__ inline double g1_rw_in(const double* tf, int lr, int lc) {
-    constexpr int MY = KY == MPBP_MG_CELL ? 4 : 3, MX = KX == MPBP_MG_CELL ? 4 : 3;
-    constexpr double WC[4] = {0.25, 0.75, 0.75, 0.25}, WN[3] = {0.5, 1.0, 0.5};
-    const double* q = tf + (2 * lr + OFF) * W + 2 * lc + OFF;
-    double acc = 0.0;
-#pragma unroll
-    for (int a = 0; a < MY; ++a)
-#pragma unroll
-        for (int b = 0; b < MX; ++b)
-            acc += ((KY == MPBP_MG_CELL ? WC[a] : WN[a]) * (KX == MPBP_MG_CELL ? WC[b] : WN[b])) * q[a * W + b];
-    return acc;
-}
-// ... over t1's window (fine block + 1)
-template <int KY, int KX, int S = kG1FW>
-__device__ inline double g1_r_in(const double* tf, int lr, int lc) { return g1_rw_in<KY, KX, S, 0>(tf, lr, lc); }
-// a tile whose transfers' windows neither wrap nor reach a 1D list's periodic special case (coarse tile of TH x TW
-// cells at (cr0, cc0), windows two coarse cells beyond it)
-__device__ inline bool g1_inner(int cr0, int cc0, int th, int tw, int nc) {
-    return cr0 >= 2 && cr0 + th + 2 <= nc && cc0 >= 2 && cc0 + tw + 2 <= nc;
-}
-// Level 1 under a row partition (PART): this rank owns coarse rows [r0, r0 + L) of every field and its level-1 vectors
-// hold them followed by h ghost rows above and below (ext_row's layout).  The tiles cover the owned rows only; every
-// value is computed in global coordinates exactly as on one GPU (the same windows, lists and rows), so the rank's rows
-// are the one-GPU launch's bits.
-struct G1Part {
-    int r0 = 0, L = 0, h = 0;
-};
-// level-1 x index of (field f, coarse row gr -- unwrapped, within two rows of the tile --, wrapped column c); window
-// rows past the ghosts (a partial last tile's) are clamped: they feed only outputs the tile does not own
-template <bool PART>
-__device__ inline int32_t g1_xidx(const G1Part& q, int nf, int f, int gr, int c, int nc) {
-    if constexpr (!PART) {
-        (void)q; (void)nf;
-        return (f * nc + (gr < 0 ? gr + nc : (gr >= nc ? gr - nc : gr))) * nc + c;
-    } else {
-        const int lr = min(max(gr - q.r0, -q.h), q.L + q.h - 1);
-        return ext_row(nf, f, lr, q.L, q.h, nc) + c;
-    }
-}
-// the level-1 row of an owned output (f, cr, cc)
-template <bool PART>
-__device__ inline int32_t g1_orow(const G1Part& q, int f, int cr, int cc, int nc) {
-    return PART ? (f * q.L + cr - q.r0) * nc + cc : (f * nc + cr) * nc + cc;
-}
-// PRO (the post-smoothing's first sweep after level 2's correction): the staged x is x + P_1 x_c, level 2's window
-// [cr0 / 2 - 2, cr0 / 2 + kGFQH - 2) x [cc0 / 2 - 2, cc0 / 2 + kGFQW - 2) staged first (k_ftile<PRO>'s scheme one level
-// down: the same P rows in window coordinates, k_mg_transfer_spmv's lists and EpiAdd's sum), and the epilogue's iterate
-// is the row's own staged value -- the prolongation launch folded in, bit-identical.
-// k_gal1's own tile: 16 x 8 coarse cells (a 32 x 16 fine block) -- its windows and t0 take 36.5 KB of LDS, so four
-// workgroups share a CU (the 32 x 4 tile's 42 KB held three), and F's rows on the block + 1 are 612 instead of 660
-constexpr int kGFW = 16, kGFH = 8;
-constexpr int kGFCW = kGFW + 4, kGFCH = kGFH + 4;               // coarse x: [c0 - 2, c0 + W + 2)
-constexpr int kGFFW = 2 * kGFW + 2, kGFFH = 2 * kGFH + 2;       // t1: fine block + 1
-constexpr int kGFPW = kGFFW + 2, kGFPH = kGFFH + 2;             // t0 and thn: fine block + 2
-constexpr int kGFQW = kGFW / 2 + 4, kGFQH = kGFH / 2 + 4;       // PRO: level 2's window (row stride kGFQW)
-constexpr int kG1QW = kG1W / 2 + 4;                             // (k_gal1p's level-2 window columns)
-template <bool INNER, class Epi, bool MAC, class XS, bool PART, bool PRO>
-__device__ __forceinline__ void gal1_run(const FStencilFast& P, const MgFields& tr, const XS& xin, const Epi& epi,
-                                         double* xs, double* ts, double* t0, double* t1, int cr0, int cc0,
-                                         const G1Part& q, const double* xc, double* xq);
-// MAC: the F hierarchy's kinds (u: rows cell-, columns node-centred; v: the reverse) at compile time
-// XS: the coarse x as staged -- XPlain (x itself) or XInit (x0 = c2_0 (b / diag): a pre-smoothing's first sweep with the
-// init pass folded in, as the grouped small levels do; the epilogue then EpiChebFirstGrp)
-template <class Epi, bool MAC = false, class XS = XPlain, bool PART = false, bool PRO = false>
-__global__ void __launch_bounds__(256) MPBP_LDS_READS k_gal1(FStencilFast P, MgFields tr, XS xin, Epi epi, G1Part q,
-                                                              const double* __restrict__ xc = nullptr) {
-    constexpr int CN = kGFCW * kGFCH, PN = kGFPW * kGFPH, FN = kGFFW * kGFFH;
-    static_assert(!PRO || (MAC && !PART), "the folded prolongation: MAC kinds, whole level");
-    __shared__ double xs[4 * CN];
-    __shared__ double ts[PN];
-    __shared__ double t0[4 * PN];
-    __shared__ double xq[PRO ? 4 * kGFQW * kGFQH : 1];
-    double* t1 = t0;
-    static_assert(FN <= PN, "t1 fits t0");
-    const int nc = P.n >> 1;
-    const int tx = (nc + kGFW - 1) / kGFW;
-    const int bk = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int cr0 = (PART ? q.r0 : 0) + (bk / tx) * kGFH, cc0 = (bk % tx) * kGFW;     // the coarse tile
-    if constexpr (MAC) {
-        if (g1_inner(cr0, cc0, kGFH, kGFW, nc)) {
-            gal1_run<true, Epi, MAC, XS, PART, PRO>(P, tr, xin, epi, xs, ts, t0, t1, cr0, cc0, q, xc, xq);
-            return;
-        }
-    }
-    gal1_run<false, Epi, MAC, XS, PART, PRO>(P, tr, xin, epi, xs, ts, t0, t1, cr0, cc0, q, xc, xq);
-}
-template <bool INNER, class Epi, bool MAC, class XS, bool PART, bool PRO>
-__device__ __forceinline__ void gal1_run(const FStencilFast& P, const MgFields& tr, const XS& xin, const Epi& epi,
-                                         double* xs, double* ts, double* t0, double* t1, int cr0, int cc0,
-                                         const G1Part& q, const double* xc, double* xq) {
-    constexpr int CN = kGFCW * kGFCH, PN = kGFPW * kGFPH, FN = kGFFW * kGFFH;
-    const int n = P.n, nc = n >> 1;
-    const int fr0 = 2 * cr0, fc0 = 2 * cc0;                      // its fine block
-    const int tid = threadIdx.x;
-    auto wrapc = [&](int a) { return a < 0 ? a + nc : (a >= nc ? a - nc : a); };
-    // a grid index to its slot in a staged window starting at virtual index `base` (the window is < the grid)
-    auto slot = [](int i, int base, int m) { int l = i - base; return l < 0 ? l + m : (l >= m ? l - m : l); };
-    {   // stage the coarse x (4 fields) and thn, every load before the first LDS store
-        constexpr int IX = (4 * CN + 255) / 256, IT = (PN + 255) / 256;
-        typename XS::Raw vx[IX];
-        double vt[IT];
-#pragma unroll
-        for (int it = 0; it < IX; ++it) {
-            const int i = tid + it * 256;
-            if (i < 4 * CN) {
-                const int f = i / CN, j = i - f * CN, r = j / kGFCW, c = j - r * kGFCW;
-                vx[it] = xin.load(g1_xidx<PART>(q, 4, f, cr0 - 2 + r, wrapc(cc0 - 2 + c), nc));
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 256;
-            if (i < PN) {
-                const int r = i / kGFPW, c = i - r * kGFPW;
-                vt[it] = P.cell[P.wrap(fr0 - 2 + r) * n + P.wrap(fc0 - 2 + c)];
-            }
-        }
-        const int n2 = nc >> 1;
-        if constexpr (PRO) {   // level 2's window first: the staged x needs it
-            auto wrap2 = [&](int a) { return a < 0 ? a + n2 : (a >= n2 ? a - n2 : a); };
-            constexpr int QF = kGFQW * kGFQH, IQ = (4 * QF + 255) / 256;
-            double vq[IQ];
-#pragma unroll
-            for (int it = 0; it < IQ; ++it) {
-                const int i = tid + it * 256;
-                if (i < 4 * QF) {
-                    const int f = i / QF, j = i - f * QF, r = j / kGFQW, c = j - r * kGFQW;
-                    vq[it] = xc[(f * n2 + wrap2((cr0 >> 1) - 2 + r)) * n2 + wrap2((cc0 >> 1) - 2 + c)];
-                }
-            }
-#pragma unroll
-            for (int it = 0; it < IQ; ++it) {
-                const int i = tid + it * 256;
-                if (i < 4 * QF) {
-                    const int f = i / QF, j = i - f * QF, r = j / kGFQW, c = j - r * kGFQW;
-                    xq[(f * kGFQH + r) * kGFQW + c] = vq[it];
-                }
-            }
-            __syncthreads();
-        }
-        const bool inner2 = PRO && g1_inner(cr0 >> 1, cc0 >> 1, kGFH / 2, kGFW / 2, n2);
-#pragma unroll
-        for (int it = 0; it < IX; ++it) {
-            const int i = tid + it * 256;
-            if (i >= 4 * CN) continue;
-            double v = xin.value(vx[it]);
-            if constexpr (PRO) {   // x + P_1 x_c (EpiAdd: the row sum, then + x)
-                const int f = i / CN, j = i - f * CN, r = j / kGFCW, c = j - r * kGFCW;
-                const double* xf = xq + f * kGFQH * kGFQW;
-                const int gr = wrapc(cr0 - 2 + r), gc = wrapc(cc0 - 2 + c), rb = (cr0 >> 1) - 2, cb = (cc0 >> 1) - 2;
-                const double pc = inner2 ? ((f & 1) ? g1_p_in<MPBP_MG_NODE, MPBP_MG_CELL, kGFQW>(xf, r, c)
-                                                    : g1_p_in<MPBP_MG_CELL, MPBP_MG_NODE, kGFQW>(xf, r, c))
-                                         : ((f & 1) ? g1_p<MPBP_MG_NODE, MPBP_MG_CELL, kGFQW>(xf, gr, gc, n2, rb, cb)
-                                                    : g1_p<MPBP_MG_CELL, MPBP_MG_NODE, kGFQW>(xf, gr, gc, n2, rb, cb));
-                v = pc + v;
-            }
-            xs[i] = v;
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it)
-            if (tid + it * 256 < PN) ts[tid + it * 256] = vt[it];
-    }
-    // the faces of this lane's t1 cells, loaded ahead (their latency behind the P_0 stage, not in the F stage)
-    constexpr int IF = (FN + 255) / 256;
-    double fu[IF], fv[IF];
-#pragma unroll
-    for (int it = 0; it < IF; ++it) {
-        const int i = tid + it * 256;
-        if (i < FN) {
-            const int r = i / kGFFW, c = i - r * kGFFW;
-            const int32_t k = P.wrap(fr0 - 1 + r) * n + P.wrap(fc0 - 1 + c);
-            fu[it] = P.uface[k];
-            fv[it] = P.vface[k];
-        }
-    }
-    __syncthreads();
-    // t0 = P_0 x on the fine block + 2
-    for (int i = tid; i < PN; i += 256) {
-        const int r = i / kGFPW, c = i - r * kGFPW;
-        const int gr = P.wrap(fr0 - 2 + r), gc = P.wrap(fc0 - 2 + c);
-        if constexpr (MAC && INNER) {
-#pragma unroll
-            for (int f = 0; f < 4; ++f)
-                t0[f * PN + i] = (f & 1) ? g1_p_in<MPBP_MG_NODE, MPBP_MG_CELL, kGFCW>(xs + f * CN, r, c)
-                                         : g1_p_in<MPBP_MG_CELL, MPBP_MG_NODE, kGFCW>(xs + f * CN, r, c);
-            continue;
-        }
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            if constexpr (MAC) {
-                t0[f * PN + i] = (f & 1)
-                    ? g1_p<MPBP_MG_NODE, MPBP_MG_CELL, kGFCW>(xs + f * CN, gr, gc, nc, cr0 - 2, cc0 - 2)
-                    : g1_p<MPBP_MG_CELL, MPBP_MG_NODE, kGFCW>(xs + f * CN, gr, gc, nc, cr0 - 2, cc0 - 2);
-                continue;
-            }
-            int yi[4], xi[4];
-            double yw[4], xw[4];
-            const int my = mg_p1d_fast(tr.ky[f], nc, gr, yi, yw), mx = mg_p1d_fast(tr.kx[f], nc, gc, xi, xw);
-            double acc = 0.0;
-            for (int a = 0; a < my; ++a) {
-                const double* xr = xs + f * CN + slot(yi[a], cr0 - 2, nc) * kGFCW;
-                for (int b = 0; b < mx; ++b) acc += (yw[a] * xw[b]) * xr[slot(xi[b], cc0 - 2, nc)];
-            }
-            t0[f * PN + i] = acc;
-        }
-    }
-    __syncthreads();
-    // t1 = F t0 on the fine block + 1
-    {
-        const TTileT<kGFPW> tt{ts, fr0 - 2, fc0 - 2};
-        const XTileT<kGFPW, kGFPH> xt{t0, fr0 - 2, fc0 - 2};
-        // t1 takes t0's LDS (63 -> 42 KB per workgroup: 3 resident per CU instead of 2): rows kept in registers until
-        // every lane has read its t0 neighbours
-        double tv[IF][4];
-#pragma unroll
-        for (int it = 0; it < IF; ++it) {
-            const int i = tid + it * 256;
-            if (i >= FN) break;
-            const int r = i / kGFFW, c = i - r * kGFFW;
-            double rd[4];
-            P.template rows4<false>(fr0 - 1 + r, fc0 - 1 + c, tt, xt, FStencilDev::Cell{{fu[it], fv[it]}}, tv[it], rd);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < IF; ++it) {
-            const int i = tid + it * 256;
-            if (i >= FN) break;
-#pragma unroll
-            for (int f = 0; f < 4; ++f) t1[f * FN + i] = tv[it][f];
-        }
-    }
-    __syncthreads();
-    // R_0 t1 on the tile's coarse rows (4 fields x 128 cells), each to the epilogue
-    if constexpr (MAC) {   // lane t: cell t & 127 of fields (t >> 7) and (t >> 7) + 2 -- one kind pair per wave
-        const int cell = tid & (kGFW * kGFH - 1), fp = tid >> 7;
-        const int cr = cr0 + cell / kGFW, cc = cc0 + cell % kGFW;
-        if (cr < (PART ? q.r0 + q.L : nc) && cc < nc) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int f = fp + 2 * h;
-                const int32_t row = g1_orow<PART>(q, f, cr, cc, nc);
-                typename Epi::P pe;
-                if constexpr (PRO) {   // the iterate is the staged x + P_1 x_c at the row
-                    pe = epi.pre_lite(row);
-                    set_x(pe, xs[f * CN + (cr - cr0 + 2) * kGFCW + (cc - cc0 + 2)]);
-                    set_diag(pe, epi.diag[row]);
-                } else {
-                    pe = epi.pre(row);
-                }
-                double acc;
-                if constexpr (INNER)
-                    acc = fp ? g1_r_in<MPBP_MG_NODE, MPBP_MG_CELL, kGFFW>(t1 + f * FN, cr - cr0, cc - cc0)
-                             : g1_r_in<MPBP_MG_CELL, MPBP_MG_NODE, kGFFW>(t1 + f * FN, cr - cr0, cc - cc0);
-                else
-                    acc = fp ? g1_r<MPBP_MG_NODE, MPBP_MG_CELL, kGFFW>(t1 + f * FN, cr, cc, n, fr0 - 1, fc0 - 1)
-                             : g1_r<MPBP_MG_CELL, MPBP_MG_NODE, kGFFW>(t1 + f * FN, cr, cc, n, fr0 - 1, fc0 - 1);
-                epi(row, acc, pe);
-            }
-        }
-        return;
-    }
-    for (int j = tid; j < 4 * kGFW * kGFH; j += 256) {
-        const int f = j / (kGFW * kGFH), cell = j - f * (kGFW * kGFH);
-        const int cr = cr0 + cell / kGFW, cc = cc0 + cell % kGFW;
-        if (cr >= (PART ? q.r0 + q.L : nc) || cc >= nc) continue;
-        const int32_t row = g1_orow<PART>(q, f, cr, cc, nc);
-        const typename Epi::P pe = epi.pre(row);
-        int yi[4], xi[4];
-        double yw[4], xw[4];
-        const int my = mg_r1d_fast(tr.ky[f], n, cr, yi, yw), mx = mg_r1d_fast(tr.kx[f], n, cc, xi, xw);
-        double acc = 0.0;
-        for (int a = 0; a < my; ++a) {
-            const double* tr1 = t1 + f * FN + slot(yi[a], fr0 - 1, n) * kGFFW;
-            for (int b = 0; b < mx; ++b) acc += (yw[a] * xw[b]) * tr1[slot(xi[b], fc0 - 1, n)];
-        }
-        epi(row, acc, pe);
-    }
-}
-
-// ---- multigrid level 0 of a tolerance-mode F hierarchy: pre-smoothing, residual and restriction in one launch ----
-// k_fpre (the V-cycle's descent at level 0, V(2, .) from x = 0): on k_fsolve's 64 x 8 tiles with H = 3 levels -- x0 =
-// c2_0 b / diag over the tile + 3, the Chebyshev sweep x1 over the tile + 2 (written out on the tile: the iterate the
-// post-smoothing continues from), the residual r = b - F x1 over the tile + 1 (in LDS), then R_0 r on the tile's 32 x 4
-// coarse cells into the coarse right-hand side.  Each value is built by the operations of the launches it replaces
-// (k_ftile<INIT>'s x0 and sweep, the residual sweep's tolerance-mode rows and EpiResid, k_mg_transfer_spmv's restriction
-// lists and product order): bit-identical to them.  HBM: b, thn and faces in, x1 and the coarse rhs out -- the residual
-// is never written.
-template <int KY, int KX, int W>
-__device__ inline double g1_rw(const double* tf, int cr, int cc, int n, int rb, int cb) {
-    constexpr int MY = KY == MPBP_MG_CELL ? 4 : 3, MX = KX == MPBP_MG_CELL ? 4 : 3;
-    int yi[4], xi[4];
-    double yw[4], xw[4];
-    mg_r1d_fast(KY, n, cr, yi, yw);
-    mg_r1d_fast(KX, n, cc, xi, xw);
-    double acc = 0.0;
-#pragma unroll
-    for (int a = 0; a < MY; ++a) {
-        const double* tr1 = tf + g1_slot(yi[a], rb, n) * W;
-#pragma unroll
-        for (int b = 0; b < MX; ++b) acc += (yw[a] * xw[b]) * tr1[g1_slot(xi[b], cb, n)];
-    }
-    return acc;
-}
-struct FPre {
-    const double* b;   // the level's right-hand side
-    double* x_out;     // x1 (the pre-smoothed iterate)
-    double* bc;        // the coarse right-hand side R_0 (b - F x1)
-    double c2_0, c1, c2;
-};
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) MPBP_LDS_READS
-k_fpre(FStencilFast P, FPre a) {
-    constexpr int H = 3;
-    using T = FsTile<H>;
-    // slots: the two tile cells (0, 1), rings 1 .. 3 (2 .. 4); ring 1 lives through the residual level, ring 2
-    // through the sweep, ring 3 is x0 only -- state (d, 1 / diag) for slots 0 .. 3
-    constexpr int NT = 2, NSL = H + 2, NS = H + 1;
-    __shared__ double ts[T::TN];
-    __shared__ double xa[4 * T::N], xb[4 * T::N];
-    const int n = P.n, nn = n * n, nc = n >> 1, ncc = nc * nc;
-    const int tx = (n + kFTW - 1) / kFTW;
-    const int bk = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int r0 = (bk / tx) * kFTH, c0 = (bk % tx) * kFTW;
-    const int rbt = r0 - H - 1, cbt = c0 - H - 1, rb = r0 - H, cb = c0 - H;
-    const int tid = threadIdx.x;
-    {
-        constexpr int IT = (T::TN + 255) / 256;
-        double v[IT];
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 256;
-            if (i < T::TN) {
-                const int sr = i / T::TW, sc = i - sr * T::TW;
-                v[it] = P.cell[P.wrap(rbt + sr) * n + P.wrap(cbt + sc)];
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 256;
-            if (i < T::TN) ts[i] = v[it];
-        }
-    }
-    const int lr = tid >> 6, lc = tid & 63;
-    int cr[NSL], cc[NSL], rr[NSL];
-    bool own[NSL];
-#pragma unroll
-    for (int m = 0; m < NT; ++m) {
-        cr[m] = r0 + lr + 4 * m; cc[m] = c0 + lc; own[m] = true; rr[m] = 0;
-    }
-#pragma unroll
-    for (int r = 1; r <= H; ++r) {
-        own[1 + r] = tid < 140 + 8 * r;
-        rr[1 + r] = r;
-        fs_ring_cell(r, own[1 + r] ? tid : 0, r0, c0, cr[1 + r], cc[1 + r]);
-    }
-    double fl[NSL][2], bl[NSL][4];
-#pragma unroll
-    for (int sl = 0; sl < NSL; ++sl) {
-        if (!own[sl]) continue;
-        const int gr = P.wrap(cr[sl]), gc = P.wrap(cc[sl]);
-        const int32_t k = gr * n + gc;
-        fl[sl][0] = P.uface[k];
-        fl[sl][1] = P.vface[k];
-#pragma unroll
-        for (int f = 0; f < 4; ++f) bl[sl][f] = a.b[(f * n + gr) * n + gc];
-    }
-    __syncthreads();
-    const TTileT<T::TW> tt{ts, rbt, cbt};
-    double d[NS][4], rd[NS][4];
-    // level 0: x0 = d0 = c2_0 b / diag over the tile + 3
-#pragma unroll
-    for (int sl = 0; sl < NSL; ++sl) {
-        if (!own[sl]) continue;
-        const int vr = cr[sl], vc = cc[sl];
-        const FStencilDev::Stage sg{{fl[sl][0], fl[sl][1]}};
-        double r4[4];
-        P.rdiag4(vr, vc, tt, sg, r4);
-        const int si = (vr - rb) * T::RW + (vc - cb);
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const double x0 = a.c2_0 * bl[sl][f] * r4[f];
-            xa[f * T::N + si] = x0;
-            if (sl < NS) {
-                d[sl][f] = x0;
-                rd[sl][f] = r4[f];
-            }
-        }
-    }
-    __syncthreads();
-    // level 1: the sweep over the tile + 2 (x1 into xb; the tile's cells also to memory)
-    {
-        const XTileT<T::RW, T::RH> xt{xa, rb, cb};
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) {
-            if (sl >= NT && (!own[sl] || rr[sl] > 2)) continue;
-            const int vr = cr[sl], vc = cc[sl];
-            double acc[4], rdx[4];
-            P.template rows4<false>(vr, vc, tt, xt, FStencilDev::Cell{{fl[sl][0], fl[sl][1]}}, acc, rdx);
-            const int si = (vr - rb) * T::RW + (vc - cb);
-#pragma unroll
-            for (int f = 0; f < 4; ++f) {
-                const double z = (bl[sl][f] - acc[f]) * rd[sl][f];
-                const double dn = a.c1 * d[sl][f] + a.c2 * z;
-                const double x = xa[f * T::N + si] + dn;
-                xb[f * T::N + si] = x;
-                if (sl < NT && vr < n && vc < n) a.x_out[f * nn + vr * n + vc] = x;
-            }
-        }
-    }
-    __syncthreads();
-    // level 2: r = b - F x1 over the tile + 1 (into xa)
-    {
-        const XTileT<T::RW, T::RH> xt{xb, rb, cb};
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) {
-            if (sl >= NT && (!own[sl] || rr[sl] > 1)) continue;
-            const int vr = cr[sl], vc = cc[sl];
-            double acc[4], rdx[4];
-            P.template rows4<false>(vr, vc, tt, xt, FStencilDev::Cell{{fl[sl][0], fl[sl][1]}}, acc, rdx);
-            const int si = (vr - rb) * T::RW + (vc - cb);
-#pragma unroll
-            for (int f = 0; f < 4; ++f) xa[f * T::N + si] = bl[sl][f] - acc[f];
-        }
-    }
-    __syncthreads();
-    // R_0 r on the tile's coarse rows (4 fields x 128 cells; the F hierarchy's MAC kinds): lane t, cell t & 127 of
-    // fields (t >> 7) and (t >> 7) + 2
-    const int cell = tid & (kG1W * kG1H - 1), fp = tid >> 7;
-    const int crr = (r0 >> 1) + cell / kG1W, ccc = (c0 >> 1) + cell % kG1W;
-    if (crr < nc && ccc < nc) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int f = fp + 2 * h;
-            const bool inner = g1_inner(r0 >> 1, c0 >> 1, kFTH / 2, kFTW / 2, nc);   // (window coordinates, slot 2 =
-                                                                                     // fine 2 c0 - 1: rb = r0 - 3)
-            const int lr = crr - (r0 >> 1), lc = ccc - (c0 >> 1);
-            const double acc =
-                inner ? (fp ? g1_rw_in<MPBP_MG_NODE, MPBP_MG_CELL, T::RW, 2>(xa + f * T::N, lr, lc)
-                            : g1_rw_in<MPBP_MG_CELL, MPBP_MG_NODE, T::RW, 2>(xa + f * T::N, lr, lc))
-                      : (fp ? g1_rw<MPBP_MG_NODE, MPBP_MG_CELL, T::RW>(xa + f * T::N, crr, ccc, n, rb, cb)
-                            : g1_rw<MPBP_MG_CELL, MPBP_MG_NODE, T::RW>(xa + f * T::N, crr, ccc, n, rb, cb));
-            a.bc[f * ncc + crr * nc + ccc] = acc;
-        }
-    }
-}
-
-// The pressure hierarchy's level 1 the same way (tolerance mode): A_1 x = R_0 (Gt_G (P_0 x)) on a 32 x 8 coarse tile
-// (a 64 x 16 fine block), one field, cell-centred both ways; Gt_G's rows by GtGStencilDev::entries and add5 (the
-// matrix-free level-0 sweep's operations), the transfers' by k_mg_transfer_spmv's: bit-identical to the three launches.
-constexpr int kG1PH2 = 8;                                     // coarse tile rows (pressure)
-constexpr int kGPFH = 2 * kG1PH2 + 2, kGPPH = kGPFH + 2;       // fine t1 / t0 rows
-// PRO: as k_gal1's (x + P_1 x_c staged, level 2's window of the 16 x 4 level-2 cells under the tile first)
-constexpr int kG1PQH = kG1PH2 / 2 + 4;   // level-2 window rows (columns kG1QW, row stride kG1CW)
-template <class Epi, class XS = XPlain, bool PART = false, bool PRO = false>
-__global__ void __launch_bounds__(256) MPBP_LDS_READS k_gal1p(GtGStencilDev P, XS xin, Epi epi, G1Part q,
-                                                               const double* __restrict__ xc = nullptr) {
-    constexpr int CH = kG1PH2 + 4, CN = kG1CW * CH, PN = kG1PW * kGPPH, FN = kG1FW * kGPFH;
-    __shared__ double xs[CN];
-    __shared__ double ts[PN];
-    __shared__ double t0[PN];
-    __shared__ double xq[PRO ? kG1CW * kG1PQH : 1];
-    static_assert(!PRO || !PART, "the folded prolongation: whole level");
-    double* t1 = t0;   // (k_gal1's aliasing: 34.7 -> 25 KB per workgroup)
-    static_assert(FN <= PN, "t1 fits t0");
-    const int n = P.n, nc = n >> 1;
-    const int tx = (nc + kG1W - 1) / kG1W;
-    const int bk = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int cr0 = (PART ? q.r0 : 0) + (bk / tx) * kG1PH2, cc0 = (bk % tx) * kG1W;
-    const int fr0 = 2 * cr0, fc0 = 2 * cc0;
-    const int tid = threadIdx.x;
-    auto wrapc = [&](int a) { return a < 0 ? a + nc : (a >= nc ? a - nc : a); };
-    {
-        constexpr int IX = (CN + 255) / 256, IT = (PN + 255) / 256;
-        typename XS::Raw vx[IX];
-        double vt[IT];
-#pragma unroll
-        for (int it = 0; it < IX; ++it) {
-            const int i = tid + it * 256;
-            if (i < CN) {
-                const int r = i / kG1CW, c = i - r * kG1CW;
-                vx[it] = xin.load(g1_xidx<PART>(q, 1, 0, cr0 - 2 + r, wrapc(cc0 - 2 + c), nc));
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it) {
-            const int i = tid + it * 256;
-            if (i < PN) {
-                const int r = i / kG1PW, c = i - r * kG1PW;
-                vt[it] = P.cell[P.wrap(fr0 - 2 + r) * n + P.wrap(fc0 - 2 + c)];
-            }
-        }
-        const int n2 = nc >> 1;
-        if constexpr (PRO) {   // level 2's window first
-            auto wrap2 = [&](int a) { return a < 0 ? a + n2 : (a >= n2 ? a - n2 : a); };
-            constexpr int QN = kG1QW * kG1PQH, IQ = (QN + 255) / 256;
-            double vq[IQ];
-#pragma unroll
-            for (int it = 0; it < IQ; ++it) {
-                const int i = tid + it * 256;
-                if (i < QN) {
-                    const int r = i / kG1QW, c = i - r * kG1QW;
-                    vq[it] = xc[wrap2((cr0 >> 1) - 2 + r) * n2 + wrap2((cc0 >> 1) - 2 + c)];
-                }
-            }
-#pragma unroll
-            for (int it = 0; it < IQ; ++it) {
-                const int i = tid + it * 256;
-                if (i < QN) {
-                    const int r = i / kG1QW, c = i - r * kG1QW;
-                    xq[r * kG1CW + c] = vq[it];
-                }
-            }
-            __syncthreads();
-        }
-        const bool inner2 = PRO && g1_inner(cr0 >> 1, cc0 >> 1, kG1PH2 / 2, kG1W / 2, n2);
-#pragma unroll
-        for (int it = 0; it < IX; ++it) {
-            const int i = tid + it * 256;
-            if (i >= CN) continue;
-            double v = xin.value(vx[it]);
-            if constexpr (PRO) {   // x + P_1 x_c (EpiAdd: the row sum, then + x)
-                const int r = i / kG1CW, c = i - r * kG1CW;
-                const double pc =
-                    inner2 ? g1_p_in<MPBP_MG_CELL, MPBP_MG_CELL>(xq, r, c)
-                           : g1_p<MPBP_MG_CELL, MPBP_MG_CELL>(xq, wrapc(cr0 - 2 + r), wrapc(cc0 - 2 + c), n2,
-                                                              (cr0 >> 1) - 2, (cc0 >> 1) - 2);
-                v = pc + v;
-            }
-            xs[i] = v;
-        }
-#pragma unroll
-        for (int it = 0; it < IT; ++it)
-            if (tid + it * 256 < PN) ts[tid + it * 256] = vt[it];
-    }
-    __syncthreads();
-    const bool inner = g1_inner(cr0, cc0, kG1PH2, kG1W, nc);   // (k_gal1's g1_*_in)
-    for (int i = tid; i < PN; i += 256) {   // t0 = P_0 x on the fine block + 2
-        const int r = i / kG1PW, c = i - r * kG1PW;
-        t0[i] = inner ? g1_p_in<MPBP_MG_CELL, MPBP_MG_CELL>(xs, r, c)
-                      : g1_p<MPBP_MG_CELL, MPBP_MG_CELL>(xs, P.wrap(fr0 - 2 + r), P.wrap(fc0 - 2 + c), nc, cr0 - 2, cc0 - 2);
-    }
-    __syncthreads();
-    {   // t1 = Gt_G t0 on the fine block + 1
-        const TTileT<kG1PW> ta{ts, fr0 - 2, fc0 - 2};
-        constexpr int IT1 = (FN + 255) / 256;
-        double tv[IT1];
-#pragma unroll
-        for (int it = 0; it < IT1; ++it) {
-            const int i0 = it * 256;
-            const int i = i0 + tid;
-            const bool live = i < FN;
-            const int ii = live ? i : 0;
-            const int r = ii / kG1FW, c = ii - r * kG1FW;
-            const int vr = fr0 - 1 + r, vc = fc0 - 1 + c, gr = P.wrap(vr), gc = P.wrap(vc);
-            const bool edge = __builtin_amdgcn_readfirstlane(__any(live && (gr == 0 || gr == n - 1 || gc == 0 ||
-                                                                            gc == n - 1))) != 0;
-            if (!live) continue;
-            double e[5];
-            P.entries(vr, vc, gr, gc, ta, e);
-            const int si = (r + 1) * kG1PW + (c + 1);
-            const double pr[5] = {e[0] * t0[si - kG1PW], e[1] * t0[si - 1], e[2] * t0[si], e[3] * t0[si + 1],
-                                  e[4] * t0[si + kG1PW]};
-            const Wrap wr{gr == 0, gr == n - 1, gc == 0, gc == n - 1};
-            tv[it] = edge ? add5<true>(0.0, pr, wr) : add5<false>(0.0, pr, wr);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < IT1; ++it)
-            if (it * 256 + tid < FN) t1[it * 256 + tid] = tv[it];
-    }
-    __syncthreads();
-    {   // R_0 t1 on the tile's 256 coarse rows, each to the epilogue
-        const int cr = cr0 + tid / kG1W, cc = cc0 + tid % kG1W;
-        if (cr < (PART ? q.r0 + q.L : nc) && cc < nc) {
-            const int32_t row = g1_orow<PART>(q, 0, cr, cc, nc);
-            typename Epi::P pe;
-            if constexpr (PRO) {   // the iterate is the staged x + P_1 x_c at the row
-                pe = epi.pre_lite(row);
-                set_x(pe, xs[(cr - cr0 + 2) * kG1CW + (cc - cc0 + 2)]);
-                set_diag(pe, epi.diag[row]);
-            } else {
-                pe = epi.pre(row);
-            }
-            epi(row, inner ? g1_r_in<MPBP_MG_CELL, MPBP_MG_CELL>(t1, cr - cr0, cc - cc0)
-                           : g1_r<MPBP_MG_CELL, MPBP_MG_CELL>(t1, cr, cc, n, fr0 - 1, fc0 - 1), pe);
-        }
-    }
-}
-
-// One thread per (slice, lane): copy the CSR row into its column-major slots.
-__global__ void k_sell_fill(Csr A, const int4* slices, int nslices, uint8_t* rlen, double* val, int32_t* col) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int sidx = (int)(t >> 6), lane = (int)(t & 63);
-    if (sidx >= nslices) return;
-    const int4 sl = slices[sidx];
-    if (lane >= sl.y) return;
-    const int32_t r = sl.x + lane;
-    const int32_t k0 = A.rp[r], len = A.rp[r + 1] - k0;
-    rlen[r] = (uint8_t)len;
-    for (int k = 0; k < len; ++k) {
-        const size_t slot = ((size_t)sl.w + (k >> 1)) * 64 + lane;
-        val[2 * slot + (k & 1)] = A.va[k0 + k];
-        col[2 * slot + (k & 1)] = A.ci[k0 + k];
-    }
-}
-
-__global__ void k_jacobi_init(int32_t n, const double* b, const double* diag, const double* sub,
-                              double* xout) {
-    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const double x = b[r] / diag[r];
-    xout[r] = sub ? sub[r] - x : x;
-}
-
-__global__ void k_cheb_init(int32_t n, const double* b, const double* diag, double c2, double* d,
-                            const double* sub, double* xout) {
-    const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const double z = b[r] / diag[r];
-    const double dn = c2 * z;
-    d[r] = dn;
-    xout[r] = sub ? sub[r] - dn : dn;
-}
-
-inline Csr to_csr(const mpbp_csr* A) { return Csr{A->row_ptr, A->col_idx, A->val, A->ncols}; }
-
-template <class Epi>
-int launch_rows(const mpbp_csr* A, const mpbp_rowblocks* blk, const double* x, Epi epi, hipStream_t st) {
-    if (!blk || blk->count <= 0) return MPBP_OK;
-    k_csr_wave<Epi><<<blk->count, kBlock, 0, st>>>(to_csr(A), x, reinterpret_cast<const int2*>(blk->pairs),
-                                                    blk->count, KO().csr_table ? blk->table : nullptr, epi);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-// Small-level CSR products through k_csr_grp: lanes per row from the mean row length (2: <= 16 entries, 4: <= 32,
-// 8: longer), so one chunk holds a multigrid coarse row (transfers 1-16 entries, Galerkin levels 20-46).
-template <class Epi, class XS = XPlain>
-int launch_grp(const mpbp_csr* A, const XS& xs, Epi epi, hipStream_t st) {
-    if (A->nrows <= 0) return MPBP_OK;
-    const int64_t avg = A->nnz / A->nrows;
-    auto go = [&](auto gc) {
-        constexpr int G = decltype(gc)::value;
-        constexpr int rpb = kBlock / G;
-        k_csr_grp<G, XS, Epi><<<(unsigned)((A->nrows + rpb - 1) / rpb), kBlock, 0, st>>>(to_csr(A), A->nrows, xs, epi);
-        MPBP_HIP(hipGetLastError());
-        return (int)MPBP_OK;
-    };
-    return avg <= 16 ? go(std::integral_constant<int, 2>{})
-                     : avg <= 32 ? go(std::integral_constant<int, 4>{}) : go(std::integral_constant<int, 8>{});
-}
-inline bool use_grp(const mpbp_csr& A) { return KO().mg_group_rows > 0 && A.nrows > 0 && A.nrows <= KO().mg_group_rows && A.nnz > 0; }
-int grp_spmv(const mpbp_csr* A, int32_t mode, const double* x, const double* z, double* y, hipStream_t st) {
-    const XPlain xs{x};
-    switch (mode) {
-    case MPBP_SPMV_STORE: return launch_grp(A, xs, EpiStore{y}, st);
-    case MPBP_SPMV_ADD: return launch_grp(A, xs, EpiAdd{z, y}, st);
-    case MPBP_SPMV_RESID: return launch_grp(A, xs, EpiResid{z, y}, st);
-    default: return set_error(MPBP_ERR_ARG, "grp_spmv: unknown mode %d", mode);
-    }
-}
-int grp_cheb(const mpbp_csr* A, const double* xin, const double* b, const double* dg, double c1, double c2, double* d,
-             const double* sub, double* xo, hipStream_t st, int store_d, bool dzero) {
-    const EpiCheb e{xin, b, dg, d, c1, c2, sub, xo, store_d};
-    const XPlain xs{xin};
-    return dzero ? launch_grp(A, xs, EpiZeroD<EpiCheb>{e}, st) : launch_grp(A, xs, e, st);
-}
-// First sweep from x = 0: x0 = d0 = c2_0 b / diag folded in (no k_cheb_init launch, same bits).
-int grp_cheb_first(const mpbp_csr* A, const double* b, const double* dg, double c2_0, double c1, double c2, double* d,
-                   const double* sub, double* xo, hipStream_t st, int store_d) {
-    EpiChebFirstGrp e;
-    static_cast<EpiChebFirst&>(e) = EpiChebFirst{b, d, c1, c2, sub, xo, store_d};
-    e.diag = dg;
-    e.c2_0 = c2_0;
-    return launch_grp(A, XInit{b, dg, c2_0}, e, st);
-}
-
-// ---- small multigrid levels with their transfers folded in (kernel option mg_fuse_small) ----
-// b_c = R (b - A x) in one launch, one wave per coarse row I: four lanes per fine row of R's row (<= 4 x 4 of them)
-// gather that row's CSR entries at once and the slot's first lane adds the products left to right from 0.0 (k_csr_grp's
-// sum) and forms b_j - sum (EpiResid); the wave's first lane then adds R's products (yw xw) r_j in list order
-// (k_mg_transfer_spmv's restriction).  The residual and restriction launches' operations, bit for bit, without r's
-// store and reload.  A fine row shared by neighbouring coarse rows is recomputed by each (up to 4x), so it pays only
-// where the two launches are latency-bound: coarse levels of <= kRrMaxCoarse rows (1024^2, mg:1, profiles/
-// r06l_mg_apply_kernel_trace.md: 7.3 vs 5.0 + 4.9 us into 1024 coarse rows, 6.6 vs ~9.8 into 256; into 4096, 10.4 vs
-// 5.1 + 4.9; into 16384, 32 vs 11 + 5).  Folding the prolongation into the first post-smoothing sweep's gathers
-// (x + P x_c per gathered column: five loads instead of one) measured slower than its two launches at every level
-// (10-31 vs 9-17 us) and is not kept.
-constexpr int32_t kRrMaxCoarse = 1024;
-constexpr int kRrL = 4, kRrJ = 12, kRrCap = kRrL * kRrJ;   // lanes per fine row, entries per lane and chunk
-__device__ inline int sel4(const int* v, int i) { return i == 0 ? v[0] : i == 1 ? v[1] : i == 2 ? v[2] : v[3]; }
-__global__ void __launch_bounds__(kBlock) k_grp_rr(Csr A, MgFields F, MgDiv dv, int32_t n, int32_t ncr,
-                                                  const double* __restrict__ x, const double* __restrict__ b,
-                                                  double* __restrict__ bc) {
-    constexpr int WPB = kBlock / 64;
-    __shared__ double prod[WPB * 16 * kRrCap];
-    __shared__ double rs[WPB * 16];
-    const int w = threadIdx.x / 64, lane = threadIdx.x % 64, s = lane / kRrL, k = lane % kRrL;
-    const int32_t I = blockIdx.x * WPB + w;   // wave-uniform: a wave past the last coarse row leaves whole
-    if (I >= ncr) return;
-    MgRow R;
-    mg_row(F, dv, n, MPBP_MG_R, I, R);
-    const bool live = s < R.my * R.mx;
-    const int a = live ? (s >= R.mx) + (s >= 2 * R.mx) + (s >= 3 * R.mx) : 0, c = s - a * R.mx;
-    const int32_t j = live ? R.off + sel4(R.yi, a) * n + sel4(R.xi, c) : 0;
-    const int32_t ks = A.rp[j], ke = live ? A.rp[j + 1] : ks;
-    const double bj = (live && k == 0) ? b[j] : 0.0;
-    double* pr = prod + (w * 16 + s) * kRrCap;
-    double acc = 0.0;
-    for (int32_t cb = ks; cb < ke; cb += kRrCap) {
-        double v[kRrJ];
-        int32_t ci[kRrJ];
-#pragma unroll
-        for (int u = 0; u < kRrJ; ++u) {
-            const int32_t e = cb + k + kRrL * u;
-            const bool in = e < ke;
-            v[u] = in ? A.va[e] : 0.0;
-            ci[u] = in ? A.ci[e] : 0;
-        }
-        double p[kRrJ];
-#pragma unroll
-        for (int u = 0; u < kRrJ; ++u) p[u] = v[u] * x[ci[u]];
-        if (cb != ks) wave_lds_sync();   // the previous chunk's sums have read their slots
-#pragma unroll
-        for (int u = 0; u < kRrJ; ++u) pr[k + kRrL * u] = p[u];
-        wave_lds_sync();
-        if (k == 0) {
-            const int32_t cnt = min(ke - cb, (int32_t)kRrCap);
-            for (int32_t e = 0; e < cnt; ++e) acc += pr[e];
-        }
-    }
-    if (live && k == 0) rs[w * 16 + s] = bj - acc;
-    wave_lds_sync();
-    if (lane == 0) {
-        double r = 0.0;
-#pragma unroll
-        for (int ya = 0; ya < 4; ++ya)
-#pragma unroll
-            for (int xb = 0; xb < 4; ++xb)
-                if (ya < R.my && xb < R.mx) r += (R.yw[ya] * R.xw[xb]) * rs[w * 16 + ya * R.mx + xb];
-        bc[I] = r;
-    }
-}
-
-// Products through the stencil-values layout (k_svl).
-inline Svl to_svl(const mpbp_svl* V) {
-    return Svl{V->nfields, V->m, V->reach, V->slots, V->delta, V->vals, V->edge_rows, V->n_edge};
-}
-int check_svl(const mpbp_svl* V, const mpbp_csr* A) {
-    if (!V || !A || V->slots < 1 || V->nfields < 1 || V->nfields * V->slots > kSvMaxDelta || V->reach < 0 ||
-        V->m < 2 * V->reach + 2 || (V->m & 1) || (V->reach & 1) || (int64_t)V->nfields * V->m * V->m != A->nrows ||
-        (int64_t)V->slots * A->nrows > INT32_MAX || !V->delta || !V->vals ||
-        V->n_edge < 0 || (V->n_edge && !V->edge_rows))
-        return set_error(MPBP_ERR_ARG, "svl: layout does not match the operator");
-    return MPBP_OK;
-}
-template <class Epi, class XS = XPlain>
-int launch_svl(const mpbp_svl* V, const mpbp_csr* A, const XS& xs, Epi epi, hipStream_t st) {
-    const int64_t w = V->m - 2 * V->reach;
-    const int64_t per = (w / 2) * w;
-    const int64_t threads = (((int64_t)V->n_edge * kSvEdgeG + kBlock - 1) / kBlock) * kBlock + V->nfields * per;
-    if (threads <= 0) return MPBP_OK;
-    k_svl<XS, Epi><<<(unsigned)((threads + kBlock - 1) / kBlock), kBlock, 0, st>>>(to_svl(V), to_csr(A), A->nrows, xs,
-                                                                                    epi);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-int svl_spmv(const mpbp_svl* V, const mpbp_csr* A, int32_t mode, const double* x, const double* z, double* y,
-             hipStream_t st) {
-    const XPlain xs{x};
-    switch (mode) {
-    case MPBP_SPMV_STORE: return launch_svl(V, A, xs, EpiStore{y}, st);
-    case MPBP_SPMV_ADD: return launch_svl(V, A, xs, EpiAdd{z, y}, st);
-    case MPBP_SPMV_RESID: return launch_svl(V, A, xs, EpiResid{z, y}, st);
-    default: return set_error(MPBP_ERR_ARG, "svl_spmv: unknown mode %d", mode);
-    }
-}
-int svl_cheb(const mpbp_svl* V, const mpbp_csr* A, const double* xin, const double* b, const double* dg, double c1,
-             double c2, double* d, const double* sub, double* xo, hipStream_t st, int store_d, bool dzero) {
-    const EpiCheb e{xin, b, dg, d, c1, c2, sub, xo, store_d};
-    const XPlain xs{xin};
-    return dzero ? launch_svl(V, A, xs, EpiZeroD<EpiCheb>{e}, st) : launch_svl(V, A, xs, e, st);
-}
-template <class Epi>
-int launch_rows_seg(const mpbp_csr* A, const mpbp_rowblocks* blk, const double* x, Epi epi, hipStream_t st) {
-    if (!blk || blk->count <= 0) return MPBP_OK;
-    k_csr_seg<Epi><<<blk->count, kBlock, 0, st>>>(to_csr(A), x, reinterpret_cast<const int2*>(blk->pairs),
-                                                   blk->count, epi);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-
-template <class Epi>
-int launch_sell(const mpbp_sell* S, const double* x, Epi epi, hipStream_t st) {
-    if (!S || S->nslices <= 0) return MPBP_OK;
-    const int slices_per_block = kBlock / 64;
-    const int grid = (S->nslices + slices_per_block - 1) / slices_per_block;
-    k_sell_rows<Epi><<<grid, kBlock, 0, st>>>(
-        Sell{reinterpret_cast<const int4*>(S->slices), S->row_len, reinterpret_cast<const double2*>(S->val),
-             reinterpret_cast<const int2*>(S->col)},
-        x, S->nslices, epi);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-
-int check_csr(const mpbp_csr* A) {
-    if (!A || !A->row_ptr || A->nrows < 0) return set_error(MPBP_ERR_ARG, "invalid csr");
-    if (A->nnz > 0 && (!A->col_idx || !A->val)) return set_error(MPBP_ERR_ARG, "csr without entries");
-    return MPBP_OK;
-}
-
-// Chebyshev-Jacobi coefficients (Saad, Iterative Methods, Alg. 12.1 with diag(A)^-1 preconditioning).
-void cheb_coeffs(double lmin, double lmax, int sweeps, double* c1, double* c2) {
-    const double theta = (lmax + lmin) / 2.0;
-    const double delta = (lmax - lmin) / 2.0;
-    const double sigma = theta / delta;
-    double rho = 1.0 / sigma;
-    c1[0] = 0.0;
-    c2[0] = 1.0 / theta;
-    for (int s = 1; s < sweeps; ++s) {
-        const double rho_new = 1.0 / (2.0 * sigma - rho);
-        c1[s] = rho_new * rho;
-        c2[s] = 2.0 * rho_new / delta;
-        rho = rho_new;
-    }
-}
-
 }  // namespace
 
-// C = alpha A B's two passes with output rows up to W entries (mpbp_spgemm_count / _fill and their wide forms)
-namespace {
-template <int W>
-int spgemm_count(const mpbp_csr* A, const mpbp_csr* B, int32_t* row_nnz, void* stream) {
-    int rc = check_csr(A);
-    if (!rc) rc = check_csr(B);
-    if (rc) return rc;
-    if (A->ncols != B->nrows) return set_error(MPBP_ERR_ARG, "spgemm: shape mismatch");
-    int* d_over = nullptr;
-    MPBP_HIP(hipMalloc(&d_over, sizeof(int)));
-    hipError_t e = hipMemsetAsync(d_over, 0, sizeof(int), as_stream(stream));
-    if (e == hipSuccess) {
-        k_spgemm_count<W><<<grid_for(A->nrows), kBlock, 0, as_stream(stream)>>>(to_csr(A), to_csr(B), A->nrows,
-                                                                             row_nnz, d_over);
-        e = hipGetLastError();
-    }
-    int h = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, d_over, sizeof(int), hipMemcpyDeviceToHost, as_stream(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
-    (void)hipFree(d_over);
-    if (e != hipSuccess) return set_error(MPBP_ERR_HIP, "spgemm_count: %s", hipGetErrorString(e));
-    if (h) return set_error(MPBP_ERR_OVERFLOW, "spgemm: %d rows wider than %d", h, W);
-    return MPBP_OK;
-}
-
-template <int W>
-int spgemm_fill(const mpbp_csr* A, const mpbp_csr* B, double alpha, const int32_t* row_ptr, int32_t* col_idx,
-                double* val, void* stream) {
-    int rc = check_csr(A);
-    if (!rc) rc = check_csr(B);
-    if (rc) return rc;
-    k_spgemm_fill<W><<<grid_for(A->nrows), kBlock, 0, as_stream(stream)>>>(to_csr(A), to_csr(B), A->nrows, alpha,
-                                                                        row_ptr, col_idx, val);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-}  // namespace
-
-// ================================================================ C ABI ====
-extern "C" {
-
-const char* mpbp_version(void) { return "libmpbp 0.1 (gfx950)"; }
-
-void mpbp_kernel_opts_default(mpbp_kernel_opts* out) {
-    if (out) *out = KO();
-}
-
-int mpbp_kernel_opts_set_thread(const mpbp_kernel_opts* o, const mpbp_kernel_opts** prev) {
-    if (int rc = check_opts(o, "kernel_opts_set_thread")) return rc;
-    if (prev) *prev = t_opts;
-    t_opts = o;
-    return MPBP_OK;
-}
-
-int mpbp_set_march_rows(int32_t rows) {
-    if (rows < 0 || rows > 4096) return set_error(MPBP_ERR_ARG, "march rows must be 0 (auto) or in [1, 4096]");
-    g_defaults.march_rows = rows;
-    return MPBP_OK;
-}
-int mpbp_set_csr_table(int32_t on) {
-    g_defaults.csr_table = on ? 1 : 0;
-    return MPBP_OK;
-}
-int mpbp_set_mg_mf_transfer(int32_t on) {
-    g_defaults.mg_mf_transfer = on ? 1 : 0;
-    return MPBP_OK;
-}
-int mpbp_set_mg_svl(int32_t on) {
-    g_defaults.mg_svl = on ? 1 : 0;
-    return MPBP_OK;
-}
-int mpbp_set_mg_group_rows(int32_t rows) {
-    if (rows < 0) return set_error(MPBP_ERR_ARG, "mg group rows must be >= 0");
-    g_defaults.mg_group_rows = rows;
-    return MPBP_OK;
-}
-int mpbp_set_pg_direct(int32_t on) {
-    g_defaults.pg_direct = on ? 1 : 0;
-    return MPBP_OK;
-}
-
-int mpbp_set_mg_galerkin_mf(int32_t on) {
-    if (on < 0 || on > 2) return set_error(MPBP_ERR_ARG, "mg_galerkin_mf must be 0, 1 or 2");
-    g_defaults.mg_galerkin_mf = on;
-    return MPBP_OK;
-}
-int mpbp_set_mg_galerkin_mf_p(int32_t on) {
-    if (on != 0 && on != 1) return set_error(MPBP_ERR_ARG, "mg_galerkin_mf_p must be 0 or 1");
-    g_defaults.mg_galerkin_mf_p = on;
-    return MPBP_OK;
-}
-int mpbp_set_f_direct(int32_t on) {
-    if (on != 0 && on != 1) return set_error(MPBP_ERR_ARG, "f_direct must be 0 or 1");
-    g_defaults.f_direct = on;
-    return MPBP_OK;
-}
-int mpbp_set_gtg_fused(int32_t on) {
-    if (on != 0 && on != 1 && on != 256 && on != 512) return set_error(MPBP_ERR_ARG, "gtg_fused must be 0, 1, 256 or 512");
-    g_defaults.gtg_fused = on != 0;
-    if (on == 256 || on == 512) g_defaults.gtg_tpb = on;
-    return MPBP_OK;
-}
-int mpbp_set_q13_sym(int32_t on) {
-    if (on != 0 && on != 1) return set_error(MPBP_ERR_ARG, "q13_sym must be 0 or 1");
-    g_defaults.q13_sym = on;
-    return MPBP_OK;
-}
-int mpbp_set_gtg_drhs(int32_t on) {
-    if (on != 0 && on != 1) return set_error(MPBP_ERR_ARG, "gtg_drhs must be 0 or 1");
-    g_defaults.gtg_drhs = on;
-    return MPBP_OK;
-}
-int mpbp_set_f_tile(int32_t on) {
-    if (on != 0 && on != 1) return set_error(MPBP_ERR_ARG, "f_tile must be 0 or 1");
-    g_defaults.f_tile = on;
-    return MPBP_OK;
-}
-int mpbp_set_f_solve(int32_t on) {
-    if (on != 0 && on != 1) return set_error(MPBP_ERR_ARG, "f_solve must be 0 or 1");
-    g_defaults.f_solve = on;
-    return MPBP_OK;
-}
-int mpbp_set_f_pair(int32_t on) {
-    if (on != 0 && on != 1) return set_error(MPBP_ERR_ARG, "f_pair must be 0 or 1");
-    g_defaults.f_pair = on;
-    return MPBP_OK;
-}
-int mpbp_set_init_diag(int32_t mode) {
-    if (mode != 0 && mode != 1) return set_error(MPBP_ERR_ARG, "init diag mode must be 0 or 1");
-    g_defaults.init_diag = mode;
-    return MPBP_OK;
-}
-const char* mpbp_last_error(void) { return g_err; }
-
-int mpbp_stokes_theta(int32_t n, double* cell, double* uface, double* vface, void* stream) {
-    if (n < 1 || !cell || !uface || !vface) return set_error(MPBP_ERR_ARG, "mpbp_stokes_theta: bad args");
-    k_theta<<<grid_for((int64_t)n * n), kBlock, 0, as_stream(stream)>>>(n, cell, uface, vface);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-
-int64_t mpbp_stokes_rows(int32_t n, int32_t op) {
-    const int64_t N = (int64_t)n * n;
-    switch (op) {
-    case MPBP_OP_A: return 5 * N;
-    case MPBP_OP_F: case MPBP_OP_G: return 4 * N;
-    case MPBP_OP_D: case MPBP_OP_D_N: case MPBP_OP_D_S: return N;
-    case MPBP_OP_L_N: case MPBP_OP_L_S: case MPBP_OP_G_N: case MPBP_OP_G_S:
-    case MPBP_OP_XI_N: case MPBP_OP_XI_S: return 2 * N;
-    default: return set_error(MPBP_ERR_ARG, "unknown operator %d", op);
-    }
-}
-
-int64_t mpbp_stokes_cols(int32_t n, int32_t op) {
-    const int64_t N = (int64_t)n * n;
-    switch (op) {
-    case MPBP_OP_A: return 5 * N;
-    case MPBP_OP_F: case MPBP_OP_D: return 4 * N;
-    case MPBP_OP_G: case MPBP_OP_G_N: case MPBP_OP_G_S: return N;
-    case MPBP_OP_L_N: case MPBP_OP_L_S: case MPBP_OP_D_N: case MPBP_OP_D_S:
-    case MPBP_OP_XI_N: case MPBP_OP_XI_S: return 2 * N;
-    default: return set_error(MPBP_ERR_ARG, "unknown operator %d", op);
-    }
-}
-
-static int make_stokes(const mpbp_stokes_params* prm, const double* cell, const double* uface,
-                       const double* vface, StokesDev* P) {
-    if (!prm || prm->n < 1 || !cell) return set_error(MPBP_ERR_ARG, "stokes: bad params");
-    if ((int64_t)prm->n * prm->n * 5 > INT32_MAX) return set_error(MPBP_ERR_OVERFLOW, "stokes: n too large");
-    *P = StokesDev{prm->n, prm->xi, prm->eta_n, prm->eta_s, prm->c, prm->d_u, prm->d_p, prm->d_div,
-                   cell, uface, vface};
-    return MPBP_OK;
-}
-
-int mpbp_stokes_count(const mpbp_stokes_params* prm, int32_t op, const double* cell,
-                      int32_t* row_nnz, void* stream) {
-    StokesDev P;
-    int rc = make_stokes(prm, cell, nullptr, nullptr, &P);
-    if (rc) return rc;
-    const int64_t rows = mpbp_stokes_rows(prm->n, op);
-    if (rows < 0) return (int)rows;
-    k_stokes_count<<<grid_for(rows), kBlock, 0, as_stream(stream)>>>(P, op, rows, row_nnz);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-
-int mpbp_stokes_fill(const mpbp_stokes_params* prm, int32_t op, const double* cell,
-                     const double* uface, const double* vface, const int32_t* row_ptr,
-                     int32_t* col_idx, double* val, void* stream) {
-    StokesDev P;
-    int rc = make_stokes(prm, cell, uface, vface, &P);
-    if (rc) return rc;
-    if ((op == MPBP_OP_A || op == MPBP_OP_F) && (!uface || !vface))
-        return set_error(MPBP_ERR_ARG, "stokes fill: A/F need face tables");
-    const int64_t rows = mpbp_stokes_rows(prm->n, op);
-    if (rows < 0) return (int)rows;
-    k_stokes_fill<<<grid_for(rows), kBlock, 0, as_stream(stream)>>>(P, op, rows, row_ptr, col_idx, val);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-
-int mpbp_stokes_count_rows(const mpbp_stokes_params* prm, int32_t op, const double* cell, const int32_t* rows,
-                           int32_t nrows, int32_t* row_nnz, void* stream) {
-    StokesDev P;
-    int rc = make_stokes(prm, cell, nullptr, nullptr, &P);
-    if (rc) return rc;
-    if (mpbp_stokes_rows(prm->n, op) < 0) return set_error(MPBP_ERR_ARG, "stokes count rows: unknown operator %d", op);
-    if (nrows < 0 || (nrows > 0 && (!rows || !row_nnz))) return set_error(MPBP_ERR_ARG, "stokes count rows: bad args");
-    if (nrows == 0) return MPBP_OK;
-    k_stokes_count<<<grid_for(nrows), kBlock, 0, as_stream(stream)>>>(P, op, nrows, row_nnz, rows);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-
-int mpbp_stokes_fill_rows(const mpbp_stokes_params* prm, int32_t op, const double* cell, const double* uface,
-                          const double* vface, const int32_t* rows, int32_t nrows, const int32_t* row_ptr,
-                          int32_t* col_idx, double* val, void* stream) {
-    StokesDev P;
-    int rc = make_stokes(prm, cell, uface, vface, &P);
-    if (rc) return rc;
-    if ((op == MPBP_OP_A || op == MPBP_OP_F) && (!uface || !vface))
-        return set_error(MPBP_ERR_ARG, "stokes fill rows: A/F need face tables");
-    if (mpbp_stokes_rows(prm->n, op) < 0) return set_error(MPBP_ERR_ARG, "stokes fill rows: unknown operator %d", op);
-    if (nrows < 0 || (nrows > 0 && (!rows || !row_ptr))) return set_error(MPBP_ERR_ARG, "stokes fill rows: bad args");
-    if (nrows == 0) return MPBP_OK;
-    k_stokes_fill<<<grid_for(nrows), kBlock, 0, as_stream(stream)>>>(P, op, nrows, row_ptr, col_idx, val, rows);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-
-int mpbp_exclusive_scan(const int32_t* row_nnz, int32_t* row_ptr, int64_t n, int64_t* total,
-                        void* stream) {
-    if (n < 0 || !row_ptr || (n > 0 && !row_nnz)) return set_error(MPBP_ERR_ARG, "scan: bad args");
-    const int64_t ntiles = (n + kScanTile - 1) / kScanTile;
-    long long* d_total = nullptr;   // [total, tile sums...]
-    MPBP_HIP(hipMalloc(&d_total, sizeof(long long) * (size_t)(1 + ntiles)));
-    hipStream_t st = as_stream(stream);
-    if (ntiles > 0) k_scan_tiles<<<(unsigned)ntiles, 256, 0, st>>>(row_nnz, n, d_total + 1);
-    k_scan_offsets<<<1, 256, 0, st>>>(d_total + 1, ntiles, row_ptr, n, d_total);
-    if (ntiles > 0) k_scan_apply<<<(unsigned)ntiles, 256, 0, st>>>(row_nnz, n, d_total + 1, row_ptr);
-    hipError_t e = hipGetLastError();
-    long long h = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, d_total, sizeof(h), hipMemcpyDeviceToHost, as_stream(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
-    (void)hipFree(d_total);
-    if (e != hipSuccess) return set_error(MPBP_ERR_HIP, "scan: %s", hipGetErrorString(e));
-    if (h > INT32_MAX) return set_error(MPBP_ERR_OVERFLOW, "scan: %lld entries exceed int32 row_ptr", h);
-    if (total) *total = h;
-    return MPBP_OK;
-}
-
-int mpbp_spgemm_count(const mpbp_csr* A, const mpbp_csr* B, int32_t* row_nnz, void* stream) {
-    return spgemm_count<kSpgemmMaxW>(A, B, row_nnz, stream);
-}
-int mpbp_spgemm_fill(const mpbp_csr* A, const mpbp_csr* B, double alpha, const int32_t* row_ptr,
-                     int32_t* col_idx, double* val, void* stream) {
-    return spgemm_fill<kSpgemmMaxW>(A, B, alpha, row_ptr, col_idx, val, stream);
-}
-int mpbp_spgemm_count_wide(const mpbp_csr* A, const mpbp_csr* B, int32_t* row_nnz, void* stream) {
-    return spgemm_count<kSpgemmWideW>(A, B, row_nnz, stream);
-}
-int mpbp_spgemm_fill_wide(const mpbp_csr* A, const mpbp_csr* B, double alpha, const int32_t* row_ptr,
-                          int32_t* col_idx, double* val, void* stream) {
-    return spgemm_fill<kSpgemmWideW>(A, B, alpha, row_ptr, col_idx, val, stream);
-}
-
-namespace {
-inline RCsr to_rcsr(const mpbp_csr* A) { return RCsr{A->row_ptr, A->col_idx, A->val, A->nrows, A->ncols, A->nnz}; }
-
-// launches k_refill<MODE> (wide: its two-entries-per-lane form) over C's rows, waits and turns the kernel's flags into
-// a return code
-int run_refill(const char* who, int mode, const mpbp_csr* X, const mpbp_csr* Y, const mpbp_csr* Z, double alpha_inner,
-               double alpha_outer, const mpbp_csr* C, void* stream, bool wide = false) {
-    if (C->nrows == 0) return MPBP_OK;
-    hipStream_t st = as_stream(stream);
-    int* d_err = nullptr;
-    MPBP_HIP(hipMalloc(&d_err, 2 * sizeof(int)));
-    hipError_t e = hipMemsetAsync(d_err, 0, 2 * sizeof(int), st);
-    if (e == hipSuccess) {
-        const unsigned grid = (unsigned)(((int64_t)C->nrows + kBlock / 64 - 1) / (kBlock / 64));
-        double* cval = const_cast<double*>(C->val);   // the one array a refill writes
-        const RCsr x = to_rcsr(X), y = to_rcsr(Y), z = Z ? to_rcsr(Z) : RCsr{nullptr, nullptr, nullptr, 0, 0, 0};
-        if (wide && mode == kRefillPair) k_refill<kRefillPair, true><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
-        else if (wide && mode == kRefillLeft) k_refill<kRefillLeft, true><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
-        else if (wide) k_refill<kRefillRight, true><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
-        else if (mode == kRefillPair) k_refill<kRefillPair><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
-        else if (mode == kRefillLeft) k_refill<kRefillLeft><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
-        else k_refill<kRefillRight><<<grid, kBlock, 0, st>>>(x, y, z, alpha_inner, alpha_outer, to_rcsr(C), cval, d_err);
-        e = hipGetLastError();
-    }
-    int h[2] = {0, 0};
-    if (e == hipSuccess) e = hipMemcpyAsync(h, d_err, sizeof(h), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(d_err);
-    if (e != hipSuccess) return set_error(MPBP_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    if (h[0] & kRefillIndex) return set_error(MPBP_ERR_ARG, "%s: %d rows hold a row extent or column index out of range", who, h[1]);
-    if (h[0] & kRefillWide)
-        return set_error(MPBP_ERR_OVERFLOW, "%s: %d rows have an output row wider than %d", who, h[1], kSpgemmWideW);
-    if (h[0] & kRefillLong)
-        return set_error(MPBP_ERR_OVERFLOW, "%s: %d rows have an %s row wider than %d", who, h[1],
-                         wide ? "inner" : "output or inner", kSpgemmMaxW);
-    if (h[0] & kRefillMissing)
-        return set_error(MPBP_ERR_PATTERN, "%s: %d rows of C lack a column their product holds", who, h[1]);
-    return MPBP_OK;
-}
-}  // namespace
-
-static int spgemm_refill(const char* who, bool wide, const mpbp_csr* A, const mpbp_csr* B, double alpha,
-                         const mpbp_csr* C, void* stream) {
-    int rc = check_csr(A);
-    if (!rc) rc = check_csr(B);
-    if (!rc) rc = check_csr(C);
-    if (rc) return rc;
-    if (A->ncols != B->nrows || C->nrows != A->nrows || C->ncols != B->ncols)
-        return set_error(MPBP_ERR_ARG, "%s: shape mismatch", who);
-    return run_refill(who, kRefillPair, A, B, nullptr, 1.0, alpha, C, stream, wide);
-}
-int mpbp_spgemm_refill(const mpbp_csr* A, const mpbp_csr* B, double alpha, const mpbp_csr* C, void* stream) {
-    return spgemm_refill("spgemm_refill", false, A, B, alpha, C, stream);
-}
-int mpbp_spgemm_refill_wide(const mpbp_csr* A, const mpbp_csr* B, double alpha, const mpbp_csr* C, void* stream) {
-    return spgemm_refill("spgemm_refill_wide", true, A, B, alpha, C, stream);
-}
-
-static int triple_refill(const char* who, bool wide, const mpbp_csr* X, const mpbp_csr* Y, const mpbp_csr* Z,
-                         int32_t assoc, double alpha_inner, double alpha_outer, const mpbp_csr* C, void* stream) {
-    int rc = check_csr(X);
-    if (!rc) rc = check_csr(Y);
-    if (!rc) rc = check_csr(Z);
-    if (!rc) rc = check_csr(C);
-    if (rc) return rc;
-    if (assoc != MPBP_ASSOC_LEFT && assoc != MPBP_ASSOC_RIGHT)
-        return set_error(MPBP_ERR_ARG, "%s: assoc must be MPBP_ASSOC_LEFT or MPBP_ASSOC_RIGHT", who);
-    if (X->ncols != Y->nrows || Y->ncols != Z->nrows || C->nrows != X->nrows || C->ncols != Z->ncols)
-        return set_error(MPBP_ERR_ARG, "%s: shape mismatch", who);
-    return run_refill(who, assoc == MPBP_ASSOC_LEFT ? kRefillLeft : kRefillRight, X, Y, Z, alpha_inner, alpha_outer, C,
-                      stream, wide);
-}
-int mpbp_triple_refill(const mpbp_csr* X, const mpbp_csr* Y, const mpbp_csr* Z, int32_t assoc, double alpha_inner,
-                       double alpha_outer, const mpbp_csr* C, void* stream) {
-    return triple_refill("triple_refill", false, X, Y, Z, assoc, alpha_inner, alpha_outer, C, stream);
-}
-int mpbp_triple_refill_wide(const mpbp_csr* X, const mpbp_csr* Y, const mpbp_csr* Z, int32_t assoc, double alpha_inner,
-                            double alpha_outer, const mpbp_csr* C, void* stream) {
-    return triple_refill("triple_refill_wide", true, X, Y, Z, assoc, alpha_inner, alpha_outer, C, stream);
-}
-
-int64_t mpbp_plan_row_blocks(const int32_t* row_ptr, int32_t row_begin, int32_t row_end,
-                             int32_t* pairs, int64_t capacity) {
-    if (!row_ptr || row_begin < 0 || row_end < row_begin) return set_error(MPBP_ERR_ARG, "plan: bad args");
-    int64_t nb = 0;
-    int32_t r = row_begin;
-    while (r < row_end) {
-        const int32_t s = r;
-        int32_t e = r;
-        while (e < row_end && e - s < kBlock && row_ptr[e + 1] - row_ptr[s] <= MPBP_BLOCK_NNZ) ++e;
-        if (e == s) e = s + 1;   // one row longer than the LDS stage
-        if (pairs && nb < capacity) {
-            pairs[2 * nb] = s;
-            pairs[2 * nb + 1] = e;
-        }
-        ++nb;
-        r = e;
-    }
-    return nb;
-}
-
-int mpbp_csr_diag(const mpbp_csr* A, int32_t col_offset, double* diag, int32_t* missing, void* stream) {
-    int rc = check_csr(A);
-    if (rc) return rc;
-    int* d_miss = nullptr;
-    MPBP_HIP(hipMalloc(&d_miss, sizeof(int)));
-    hipError_t e = hipMemsetAsync(d_miss, 0, sizeof(int), as_stream(stream));
-    if (e == hipSuccess) {
-        k_csr_diag<<<grid_for(A->nrows), kBlock, 0, as_stream(stream)>>>(to_csr(A), A->nrows, col_offset,
-                                                                      diag, d_miss);
-        e = hipGetLastError();
-    }
-    int h = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, d_miss, sizeof(int), hipMemcpyDeviceToHost, as_stream(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
-    (void)hipFree(d_miss);
-    if (e != hipSuccess) return set_error(MPBP_ERR_HIP, "csr_diag: %s", hipGetErrorString(e));
-    if (missing) *missing = h;
-    return MPBP_OK;
-}
-
-int mpbp_gershgorin(const mpbp_csr* A, const double* diag, double* lmax, void* stream) {
-    int rc = check_csr(A);
-    if (rc) return rc;
-    unsigned long long* d_out = nullptr;
-    MPBP_HIP(hipMalloc(&d_out, sizeof(unsigned long long)));
-    hipError_t e = hipMemsetAsync(d_out, 0, sizeof(unsigned long long), as_stream(stream));
-    if (e == hipSuccess) {
-        k_gershgorin<<<grid_for(A->nrows), kBlock, 0, as_stream(stream)>>>(to_csr(A), A->nrows, diag, d_out);
-        e = hipGetLastError();
-    }
-    unsigned long long h = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, d_out, sizeof(h), hipMemcpyDeviceToHost, as_stream(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
-    (void)hipFree(d_out);
-    if (e != hipSuccess) return set_error(MPBP_ERR_HIP, "gershgorin: %s", hipGetErrorString(e));
-    double v;
-    memcpy(&v, &h, sizeof(v));
-    if (lmax) *lmax = v;
-    return MPBP_OK;
-}
-
-int mpbp_csr_extract_count(const mpbp_csr* A, const int32_t* rows, int32_t nrows_local,
-                           int32_t* row_nnz, void* stream) {
-    int rc = check_csr(A);
-    if (rc) return rc;
-    if (nrows_local < 0 || (nrows_local && (!rows || !row_nnz))) return set_error(MPBP_ERR_ARG, "extract: bad args");
-    if (nrows_local == 0) return MPBP_OK;
-    k_extract_count<<<grid_for(nrows_local), kBlock, 0, as_stream(stream)>>>(to_csr(A), rows, nrows_local, row_nnz);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-
-int mpbp_csr_extract_fill(const mpbp_csr* A, const int32_t* rows, int32_t nrows_local,
-                          const int32_t* colmap, const int32_t* row_ptr_local, int32_t* col_local,
-                          double* val_local, void* stream) {
-    int rc = check_csr(A);
-    if (rc) return rc;
-    if (nrows_local == 0) return MPBP_OK;
-    int* d_bad = nullptr;
-    MPBP_HIP(hipMalloc(&d_bad, sizeof(int)));
-    hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(int), as_stream(stream));
-    if (e == hipSuccess) {
-        k_extract_fill<<<grid_for(nrows_local), kBlock, 0, as_stream(stream)>>>(
-            to_csr(A), rows, nrows_local, colmap, row_ptr_local, col_local, val_local, d_bad);
-        e = hipGetLastError();
-    }
-    int h = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, d_bad, sizeof(int), hipMemcpyDeviceToHost, as_stream(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
-    (void)hipFree(d_bad);
-    if (e != hipSuccess) return set_error(MPBP_ERR_HIP, "extract_fill: %s", hipGetErrorString(e));
-    if (h) return set_error(MPBP_ERR_PATTERN, "extract: %d entries reference columns outside the halo", h);
-    return MPBP_OK;
-}
-
-int mpbp_spmv(const mpbp_csr* A, const mpbp_rowblocks* blocks, int32_t mode, const double* x,
-              const double* z, double* y, void* stream) {
-    int rc = check_csr(A);
-    if (rc) return rc;
-    if (!x || !y || (mode != MPBP_SPMV_STORE && !z)) return set_error(MPBP_ERR_ARG, "spmv: bad vectors");
-    const hipStream_t st = as_stream(stream);
-    switch (mode) {
-    case MPBP_SPMV_STORE: return launch_rows(A, blocks, x, EpiStore{y}, st);
-    case MPBP_SPMV_ADD: return launch_rows(A, blocks, x, EpiAdd{z, y}, st);
-    case MPBP_SPMV_RESID: return launch_rows(A, blocks, x, EpiResid{z, y}, st);
-    default: return set_error(MPBP_ERR_ARG, "spmv: unknown mode %d", mode);
-    }
-}
-
-int mpbp_hbm_stream(const void* src, int64_t bytes, int32_t mode, double* dst, void* stream) {
-    if (!src || !dst || bytes < 16 || (mode != 0 && mode != 1)) return set_error(MPBP_ERR_ARG, "hbm_stream: bad args");
-    const hipStream_t st = as_stream(stream);
-    if (mode == 0) {
-        const int64_t n16 = bytes / 16;
-        k_hbm_read<<<(unsigned)((n16 + 1023) / 1024), kBlock, 0, st>>>(reinterpret_cast<const f64x2*>(src), n16, dst);
-    } else {
-        const int64_t nwaves = bytes / (576 * 16);
-        if (nwaves < 1) return set_error(MPBP_ERR_ARG, "hbm_stream: mode 1 needs >= 9 KiB");
-        k_hbm_readwrite<<<(unsigned)((nwaves + 3) / 4), kBlock, 0, st>>>(reinterpret_cast<const f64x2*>(src), nwaves,
-                                                                         dst);
-    }
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-
-int mpbp_spmv_seg(const mpbp_csr* A, const mpbp_rowblocks* blocks, int32_t mode, const double* x,
-                  const double* z, double* y, void* stream) {
-    int rc = check_csr(A);
-    if (rc) return rc;
-    if (!x || !y || (mode != MPBP_SPMV_STORE && !z)) return set_error(MPBP_ERR_ARG, "spmv_seg: bad vectors");
-    const hipStream_t st = as_stream(stream);
-    switch (mode) {
-    case MPBP_SPMV_STORE: return launch_rows_seg(A, blocks, x, EpiStore{y}, st);
-    case MPBP_SPMV_ADD: return launch_rows_seg(A, blocks, x, EpiAdd{z, y}, st);
-    case MPBP_SPMV_RESID: return launch_rows_seg(A, blocks, x, EpiResid{z, y}, st);
-    default: return set_error(MPBP_ERR_ARG, "spmv_seg: unknown mode %d", mode);
-    }
-}
-
-int mpbp_jacobi_init(int32_t nrows, const double* b, const double* diag, const double* sub,
-                     double* x_out, void* stream) {
-    if (nrows < 0 || (nrows && (!b || !diag || !x_out))) return set_error(MPBP_ERR_ARG, "jacobi_init: bad args");
-    if (!nrows) return MPBP_OK;
-    k_jacobi_init<<<grid_for(nrows), kBlock, 0, as_stream(stream)>>>(nrows, b, diag, sub, x_out);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-
-int mpbp_jacobi_step(const mpbp_csr* A, const mpbp_rowblocks* blocks, const double* x_in,
-                     const double* b, const double* diag, const double* sub, double* x_out,
-                     void* stream) {
-    int rc = check_csr(A);
-    if (rc) return rc;
-    if (!x_in || !b || !diag || !x_out || x_in == x_out) return set_error(MPBP_ERR_ARG, "jacobi_step: bad vectors");
-    return launch_rows(A, blocks, x_in, EpiJacobi{x_in, b, diag, sub, x_out}, as_stream(stream));
-}
-
-int mpbp_cheb_init(int32_t nrows, const double* b, const double* diag, double c2, double* d,
-                   const double* sub, double* x_out, void* stream) {
-    if (nrows < 0 || (nrows && (!b || !diag || !d || !x_out))) return set_error(MPBP_ERR_ARG, "cheb_init: bad args");
-    if (!nrows) return MPBP_OK;
-    k_cheb_init<<<grid_for(nrows), kBlock, 0, as_stream(stream)>>>(nrows, b, diag, c2, d, sub, x_out);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-
-static int cheb_step_impl(const mpbp_csr* A, const mpbp_rowblocks* blocks, const double* x_in,
-                          const double* b, const double* diag, double c1, double c2, double* d,
-                          const double* sub, double* x_out, void* stream, int store_d) {
-    int rc = check_csr(A);
-    if (rc) return rc;
-    if (!x_in || !b || !diag || !d || !x_out || x_in == x_out) return set_error(MPBP_ERR_ARG, "cheb_step: bad vectors");
-    return launch_rows(A, blocks, x_in, EpiCheb{x_in, b, diag, d, c1, c2, sub, x_out, store_d}, as_stream(stream));
-}
-
-int mpbp_cheb_step(const mpbp_csr* A, const mpbp_rowblocks* blocks, const double* x_in,
-                   const double* b, const double* diag, double c1, double c2, double* d,
-                   const double* sub, double* x_out, void* stream) {
-    return cheb_step_impl(A, blocks, x_in, b, diag, c1, c2, d, sub, x_out, stream, 1);
-}
-
-int mpbp_cheb_coeffs(double lmin, double lmax, int32_t sweeps, double* c1, double* c2) {
-    if (sweeps < 1 || !c1 || !c2 || !(lmax > lmin) || !(lmin >= 0.0))
-        return set_error(MPBP_ERR_ARG, "cheb_coeffs: need sweeps >= 1 and lmax > lmin >= 0");
-    cheb_coeffs(lmin, lmax, sweeps, c1, c2);
-    return MPBP_OK;
-}
-
-int mpbp_gather(int32_t count, const int32_t* idx, const double* src, double* dst, void* stream) {
-    if (count <= 0) return MPBP_OK;
-    k_gather<<<grid_for(count), kBlock, 0, as_stream(stream)>>>(count, idx, src, dst);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-
-int mpbp_scatter(int32_t count, const int32_t* idx, const double* src, double* dst, void* stream) {
-    if (count <= 0) return MPBP_OK;
-    k_scatter<<<grid_for(count), kBlock, 0, as_stream(stream)>>>(count, idx, src, dst);
-    MPBP_HIP(hipGetLastError());
-    return MPBP_OK;
-}
-
-int mpbp_event_create(void** ev) {
-    hipEvent_t e;
-    MPBP_HIP(hipEventCreate(&e));
-    *ev = (void*)e;
-    return MPBP_OK;
-}
-
-int mpbp_event_create_scoped(void** ev, int32_t device_scope) {
-    hipEvent_t e;
-    MPBP_HIP(hipEventCreateWithFlags(&e, device_scope ? hipEventReleaseToDevice : hipEventDefault));
-    *ev = (void*)e;
-    return MPBP_OK;
-}
-
-int mpbp_event_record(void* ev, void* stream) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    MPBP_HIP(hipStreamIsCapturing(as_stream(stream), &cs));
-    if (cs == hipStreamCaptureStatusNone) MPBP_HIP(hipEventRecord((hipEvent_t)ev, as_stream(stream)));
-    return MPBP_OK;
-}
-
-int mpbp_event_destroy(void* ev) {
-    MPBP_HIP(hipEventDestroy((hipEvent_t)ev));
-    return MPBP_OK;
-}
-
-int mpbp_event_elapsed_ms(void* start, void* stop, float* ms) {
-    MPBP_HIP(hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)stop));
-    return MPBP_OK;
-}
-
-}  // extern "C"
-
+#include "f_tile.inc"
+#include "f_solve_w.inc"
+#include "pg_stencil.inc"
+#include "gtg_solve.inc"
+#include "mg_fused.inc"
+#include "launchers.inc"
+#include "abi_core.inc"
 #include "krylov.inc"
 #include "abi_stencil.inc"
 #include "q13.inc"

@@ -1,6 +1,6 @@
 // Gt_F_G on the 13-point diamond: the diamond-layout kernels, k_qmf (matrix-free, tolerance mode) and the svl / q13
-// C ABI.  Needs mpbp.hip's kernel sections (Csr, the epilogues, FStencilFast, XTileT / TTileT, PGDev, svl_spmv /
-// svl_cheb) and abi_stencil.inc (make_fstencil, make_pgstencil).
+// C ABI.  Needs mpbp.hip's Csr, epilogues and FStencilFast, XTileT / TTileT (f_tile.inc), PGDev (pg_stencil.inc),
+// svl_spmv / svl_cheb (launchers.inc) and abi_stencil.inc (make_fstencil, make_pgstencil).
 // A fragment of mpbp.hip, included there once and in order: not a self-contained header.
 
 // ================================================ Gt_F_G, 13-point diamond ====

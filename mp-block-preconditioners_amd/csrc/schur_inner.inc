@@ -1,6 +1,7 @@
 // The pressure side's fused launches (d_rhs_x0, launch_gtg_solve_t, gtg_fused_ok, gtg_solve_fused), closing the
 // namespace schur_ops.inc opened; their C entry mpbp_gtg_stencil_cheb_solve; then the Schur apply's inner solves
-// (f_pair, inner_solve, f_solve_gx).  Needs schur_ops.inc and mpbp.hip's k_gtg_solve and F launchers.
+// (f_pair, inner_solve, f_solve_gx).  Needs schur_ops.inc, k_gtg_solve (gtg_solve.inc) and the F launchers
+// (f_tile.inc, f_solve_w.inc).
 // A fragment of mpbp.hip, included there once and in order: not a self-contained header.
 namespace {
 

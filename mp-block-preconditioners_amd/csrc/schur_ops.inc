@@ -1,6 +1,6 @@
 // The Schur apply's operators: Ctx, OpRef / OpPair, MgGal, op_spmv / op_init / op_first_sweep / op_cheb /
-// op_jacobi and two_phase.  Opens the namespace that schur_inner.inc closes.  Needs mpbp.hip's kernels and
-// launchers, the C entries of its "C ABI" section (mpbp_spmv, mpbp_cheb_init, ...) and abi_stencil.inc.
+// op_jacobi and two_phase.  Opens the namespace that schur_inner.inc closes.  Needs mpbp.hip's kernels, the kernel
+// fragments and launchers.inc, the C entries of abi_core.inc (mpbp_spmv, mpbp_cheb_init, ...) and abi_stencil.inc.
 // A fragment of mpbp.hip, included there once and in order: not a self-contained header.
 
 // ======================================================= Schur apply ====

@@ -41,7 +41,7 @@ class Inner:
 
 
 def cheb_coeffs(lmin, lmax, sweeps):
-    """Chebyshev-Jacobi coefficients; same expressions as mpbp.hip cheb_coeffs."""
+    """Chebyshev-Jacobi coefficients; same expressions as csrc/launchers.inc's cheb_coeffs."""
     theta = (lmax + lmin) / 2.0
     delta = (lmax - lmin) / 2.0
     sigma = theta / delta

@@ -13,8 +13,8 @@ Coefficient sets (xi, eta_n, eta_s, c, d_u, d_p):
 thn fields: "ref" (oracle.stokes_oracle.theta_tables) and "random" (three independent uniform(0.2, 0.8) tables,
 default_rng(1000 + n): test_gpu_refresh._tables' random field).
 
-Kernels, their gates (csrc/: fsolve_ok and ftile_ok in mpbp.hip, gtg_fused_ok in schur_inner.inc, fpre_ok and gpre_ok in
-mg_solve.inc, gal_fused_ok and gal_pro_ok in schur_ops.inc) and the sizes that take them here:
+Kernels, their gates (csrc/: ftile_ok in f_tile.inc, fsolve_ok in f_solve_w.inc, gtg_fused_ok in schur_inner.inc,
+fpre_ok and gpre_ok in mg_solve.inc, gal_fused_ok and gal_pro_ok in schur_ops.inc) and the sizes that take them here:
   k_fsolve / k_fsolve_w   fsolve_ok: 3 updates n >= 70 (FsTile<2>::TW), 4 updates n >= 72 (FsTile<3>::TW); needs f_pair
                           -> kf = 3, 4 at n = 72, 76, 100, both tile forms (f_solve_tile 0: 64 x 8, 1: 32 x 16)
   k_ftile                 ftile_ok: n >= kFTW + kFTH + 4 = 76 -> n = 76, 100 (x0 + sweep 1 for every kf; the last pair

@@ -308,7 +308,24 @@ typedef struct mpbp_schur_plan {
                                         sweeps' rows (inner solves, multigrid level 0 smoothing and residuals) */
     const struct mpbp_kernel_opts* opts; /* optional: this plan's kernel choices (NULL: the process defaults); they
                                         also govern the plan's multigrid hierarchies inside the apply */
+    /* Which block form of A = [[F, G], [-D, 0]] the apply inverts, with S the approximate Schur complement whose
+     * inverse is S~^-1 = Gt_G^-1 Gt_F_G Gt_G^-1 (solve.py:265-271) and every ^-1 the plan's inner solve from x0 = 0:
+     *   MPBP_FORM_FULL (0, a zero-initialised plan): the block-LU product [[F, 0], [-D, S]] [[I, F^-1 G], [0, I]],
+     *       approx_schur_op as written (solve.py:257-277): two F solves.
+     *   MPBP_FORM_UPPER:    [[F, G], [0, S]], the matrix compute_preconditioned_A builds (solve.py:191-196):
+     *       x_p = S~^-1 v_p ; u = F^-1 (v_u - G x_p).  One F solve.
+     *   MPBP_FORM_LOWER:    [[F, 0], [-D, S]]: u = F^-1 v_u ; x_p = S~^-1 (D u + v_p) (solve.py:258-271, then stop:
+     *       x_p is the full form's bit for bit).  One F solve, no G.
+     *   MPBP_FORM_DIAGONAL: [[F, 0], [0, S]]: u = F^-1 v_u ; x_p = S~^-1 v_p.  One F solve, neither D nor G.
+     * Each returns [u, x_p].  One GPU only: a plan with halo set and form != FULL is refused.  With fuse_g the upper
+     * form's F solve builds its right-hand side v_u - G x_p per cell inside the whole-solve launch (fast numerics,
+     * Chebyshev F of 3 or 4 sweeps; bit-identical to the G launch in MPBP_SPMV_RESID mode followed by the solve). */
+    int32_t form;
 } mpbp_schur_plan;
+#define MPBP_FORM_FULL 0
+#define MPBP_FORM_UPPER 1
+#define MPBP_FORM_LOWER 2
+#define MPBP_FORM_DIAGONAL 3
 
 const char* mpbp_version(void);
 const char* mpbp_last_error(void);
@@ -444,8 +461,8 @@ int mpbp_cheb_step(const mpbp_csr* A, const mpbp_rowblocks* blocks, const double
                    const double* sub, double* x_out, void* stream);
 /* Chebyshev coefficients used by mpbp_schur_apply for sweep s (0-based): c1[s], c2[s]. Host. */
 int mpbp_cheb_coeffs(double lmin, double lmax, int32_t sweeps, double* c1, double* c2);
-/* out = M^-1 v with M the block upper-triangular approximate-commutator preconditioner
- * (solve.py:257-277): v, out are device vectors of nu + np owned entries. */
+/* out = M^-1 v with M the approximate-commutator block preconditioner in the plan's form (mpbp_schur_plan.form;
+ * FULL: the block-LU apply of solve.py:257-277): v, out are device vectors of nu + np owned entries, out apart from v. */
 /* Multigrid level 1 of the plan's F (kind MPBP_VEC_VELOCITY) or Gt_G (MPBP_VEC_PRESSURE) hierarchy, y = op(A_1 x) (modes
  * as mpbp_spmv), as the ONE fused matrix-free launch the tolerance-mode multigrid apply runs (k_gal1 / k_gal1p:
  * R_0 (A_0 (P_0 x))).  One GPU, plan f_numerics FAST, kernel option mg_galerkin_mf = 2 (else MPBP_ERR_ARG).  For timing. */

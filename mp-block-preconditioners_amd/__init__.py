@@ -6,7 +6,7 @@ from ._lib import MpbpError, lib
 from .csr import DeviceCSR, DeviceSELL, spgemm
 from .mg import FIELDS_PRESSURE, FIELDS_VELOCITY, Multigrid
 from .preconditioner import MultiphaseBlockPreconditioner, StokesOperator, thn, ths
-from .solve import (ApproxSchurPreconditioner, InnerSolver, fgmres, print_true_res_norm,
+from .solve import (FORMS, ApproxSchurPreconditioner, InnerSolver, fgmres, print_true_res_norm,
                     solve_with_approx_schur_pc, solve_without_pc)
 from .distributed import DistributedStokesOperator
 from .utils import (fill_sol_and_RHS_vecs, manufactured_problem, manufactured_problem_constant, max_norm, print_norms, weighted_L1,
@@ -15,7 +15,7 @@ from .utils import (fill_sol_and_RHS_vecs, manufactured_problem, manufactured_pr
 __all__ = [
     "MpbpError", "lib", "DeviceCSR", "DeviceSELL", "spgemm", "MultiphaseBlockPreconditioner", "StokesOperator", "thn",
     "ths",
-    "ApproxSchurPreconditioner", "InnerSolver", "fgmres", "print_true_res_norm",
+    "ApproxSchurPreconditioner", "FORMS", "InnerSolver", "fgmres", "print_true_res_norm",
     "solve_with_approx_schur_pc", "solve_without_pc", "fill_sol_and_RHS_vecs", "manufactured_problem", "manufactured_problem_constant", "max_norm",
     "print_norms", "weighted_L1", "weighted_L2", "Multigrid", "FIELDS_VELOCITY", "FIELDS_PRESSURE",
     "DistributedStokesOperator",

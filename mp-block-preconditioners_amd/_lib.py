@@ -17,6 +17,7 @@ OK, ERR_ARG = 0, -1                    # mpbp.h return codes (MPBP_OK, MPBP_ERR_
 ERR_OVERFLOW = -3                     # MPBP_ERR_OVERFLOW
 SPMV_FAST = 0x100                     # mpbp_f_stencil_spmv: tolerance-mode F rows
 NUMERICS_EXACT, NUMERICS_FAST = 0, 1  # mpbp_schur_plan.f_numerics
+FORM_FULL, FORM_UPPER, FORM_LOWER, FORM_DIAGONAL = 0, 1, 2, 3  # mpbp_schur_plan.form
 INNER_JACOBI, INNER_CHEBYSHEV, INNER_MG = 0, 1, 2
 ASSOC_LEFT, ASSOC_RIGHT = 0, 1        # mpbp_triple_refill: (X Y) Z or X (Y Z)
 MG_CELL, MG_NODE = 0, 1
@@ -167,7 +168,7 @@ class SchurPlan(Structure):
                 ("halo_first", c_int32), ("ca", c_int32), ("ca_reach_q", c_int32), ("wu_ext", c_void_p),
                 ("diag_F_ext", c_void_p), ("diag_P_ext", c_void_p), ("halo_pair", HALO_PAIR_FN),
                 ("q13", c_void_p), ("q13_n", c_int32), ("mg_F", POINTER(Mg)), ("mg_P", POINTER(Mg)),
-                ("fuse_g", c_int32), ("f_numerics", c_int32), ("opts", POINTER(KernelOpts))]
+                ("fuse_g", c_int32), ("f_numerics", c_int32), ("opts", POINTER(KernelOpts)), ("form", c_int32)]
 
 
 _P = c_void_p

@@ -169,7 +169,9 @@ k_fsolve_w(FStencilFast P, FSolve a, BS bs) {
     auto own = [&](int sl) { return sl < NT || (sl == NT ? rA != 0 : ownB); };
     // one wrapped (gr, gc) and k = gr n + gc per cell: faces, b, sub and the output (a tile cell inside the grid is
     // its own wrapped cell) index from it: a 32-bit byte offset from the field's base (n n 8 < 2^32)
-    double fl[NSL][2], bl[BS::on ? 1 : NSL][4];
+    constexpr bool LB = !BS::on || BS::resid;   // b (BNone) or z (GxR) loaded per owned cell
+    static_assert(!(BS::resid && (PART || SUB)), "GxR: one GPU, no sub");
+    double fl[NSL][2], bl[LB ? NSL : 1][4];
     uint32_t kg[NSL];
     bool ww[NSL], wn[NSL], outok[NT];
 #pragma unroll
@@ -185,7 +187,10 @@ k_fsolve_w(FStencilFast P, FSolve a, BS bs) {
         if (sl < NT) outok[sl < NT ? sl : 0] = vr < hi && vc < n;   // else a tile past the last row / column
         fl[sl][0] = ld_off(P.uface, kg[sl]);
         fl[sl][1] = ld_off(P.vface, kg[sl]);
-        if constexpr (!BS::on) {
+        if constexpr (BS::resid) {
+#pragma unroll
+            for (int f = 0; f < 4; ++f) bl[sl][f] = ld_off(bs.z + (size_t)f * nn, kg[sl]);
+        } else if constexpr (!BS::on) {
             if constexpr (PART) {
                 const int br = in_row(vr, P.h);
 #pragma unroll
@@ -230,7 +235,10 @@ k_fsolve_w(FStencilFast P, FSolve a, BS bs) {
             const int pi = ki + PW + 1;
             const typename BS::Q q{ps[pi], ps[pi - 1], ps[pi - PW]};
 #pragma unroll
-            for (int f = 0; f < 4; ++f) b4[f] = bs.b_at(f, 0, 0, ww[sl], wn[sl], TRelT<T::TSW>{t}, q);
+            for (int f = 0; f < 4; ++f) {
+                b4[f] = bs.b_at(f, 0, 0, ww[sl], wn[sl], TRelT<T::TSW>{t}, q);
+                if constexpr (BS::resid) b4[f] = bl[sl][f] - b4[f];   // z - (G x_p), EpiResid's subtraction
+            }
         } else {
 #pragma unroll
             for (int f = 0; f < 4; ++f) b4[f] = bl[sl][f];
@@ -317,8 +325,13 @@ int launch_fsolve_w(const FStencilFast& P, const FSolve& a, hipStream_t st, cons
     constexpr int TW = 32, TH = 16;
     const int rows = PART ? P.L + 2 * P.ext : P.n;
     const int64_t tiles = (int64_t)((P.n + TW - 1) / TW) * ((rows + TH - 1) / TH);
+    if constexpr (BS::resid) {   // GxR: the upper block form's solve, never subtracted from anything
+        if (a.sub) return set_error(MPBP_ERR_ARG, "fsolve: the z - G x_p right-hand side takes no sub");
+        k_fsolve_w<TW, TH, H, false, PART, BS><<<(unsigned)tiles, 256, 0, st>>>(P, a, bs);
+    } else {
     if (a.sub) k_fsolve_w<TW, TH, H, true, PART, BS><<<(unsigned)tiles, 256, 0, st>>>(P, a, bs);
     else k_fsolve_w<TW, TH, H, false, PART, BS><<<(unsigned)tiles, 256, 0, st>>>(P, a, bs);
+    }
     MPBP_HIP(hipGetLastError());
     return MPBP_OK;
 }
@@ -341,6 +354,9 @@ int launch_fsolve(const FStencilDev& Pd, int K, const double* c1, const double* 
         (part && (P.which != 3 || P.h < P.ext + K - 1 || P.oh < P.ext || (BS::on && xp_h < P.ext + K))))
         return set_error(MPBP_ERR_ARG, "fsolve: one GPU whole grid, or owned + ext rows with b ext + K - 1 deep");
     if (!x_out || (!BS::on && !b) || x_out == b) return set_error(MPBP_ERR_ARG, "fsolve: bad vectors");
+    if constexpr (BS::resid) {
+        if (!bs.z || bs.z == x_out || part) return set_error(MPBP_ERR_ARG, "fsolve: z - G x_p needs z apart from x, one GPU");
+    }
     FSolve a{b, sub, x_out, c2[0], {}, {}};
     for (int l = 1; l < K; ++l) {
         a.c1[l - 1] = c1[l];

@@ -391,7 +391,9 @@ k_fsolve(FStencilFast P, FSolve a, BS bs) {
     }
     // every owned cell's faces and b (BNone) are loaded here, behind the staging loads and ahead of the barrier: one
     // global-memory latency for the whole level 0 instead of one per cell
-    double fl[NSL][2], bl[BS::on ? 1 : NSL][4];
+    constexpr bool LB = !BS::on || BS::resid;   // b (BNone) or z (GxR) loaded per owned cell
+    static_assert(!(BS::resid && (PART || SUB)), "GxR: one GPU, no sub");
+    double fl[NSL][2], bl[LB ? NSL : 1][4];
 #pragma unroll
     for (int sl = 0; sl < NSL; ++sl) {
         if (!own[sl]) continue;
@@ -399,7 +401,10 @@ k_fsolve(FStencilFast P, FSolve a, BS bs) {
         const int32_t k = gr * n + gc;
         fl[sl][0] = P.uface[k];
         fl[sl][1] = P.vface[k];
-        if constexpr (!BS::on) {
+        if constexpr (BS::resid) {
+#pragma unroll
+            for (int f = 0; f < 4; ++f) bl[sl][f] = bs.z[(f * n + gr) * n + gc];
+        } else if constexpr (!BS::on) {
             const int br = in_row(cr[sl], P.h);
 #pragma unroll
             for (int f = 0; f < 4; ++f) bl[sl][f] = a.b[(PART ? ext_row(4, f, br, P.L, P.h, n) : (f * n + br) * n) + gc];
@@ -421,7 +426,10 @@ k_fsolve(FStencilFast P, FSolve a, BS bs) {
             const int pi = (vr - rb + 1) * PW + (vc - cb + 1);
             const typename BS::Q q{ps[pi], ps[pi - 1], ps[pi - PW]};
 #pragma unroll
-            for (int f = 0; f < 4; ++f) b4[f] = bs.b_at(f, vr, vc, gc == 0, gr == 0, tt, q);
+            for (int f = 0; f < 4; ++f) {
+                b4[f] = bs.b_at(f, vr, vc, gc == 0, gr == 0, tt, q);
+                if constexpr (BS::resid) b4[f] = bl[sl][f] - b4[f];   // z - (G x_p), EpiResid's subtraction
+            }
         } else {
 #pragma unroll
             for (int f = 0; f < 4; ++f) b4[f] = bl[sl][f];
@@ -499,8 +507,13 @@ template <int H, bool PART, class BS>
 int launch_fsolve_t(const FStencilFast& P, const FSolve& a, hipStream_t st, const BS& bs) {
     const int rows = PART ? P.L + 2 * P.ext : P.n;
     const int64_t tiles = (int64_t)((P.n + kFTW - 1) / kFTW) * ((rows + kFTH - 1) / kFTH);
+    if constexpr (BS::resid) {   // GxR: the upper block form's solve, never subtracted from anything
+        if (a.sub) return set_error(MPBP_ERR_ARG, "fsolve: the z - G x_p right-hand side takes no sub");
+        k_fsolve<H, false, PART, BS><<<(unsigned)tiles, 256, 0, st>>>(P, a, bs);
+    } else {
     if (a.sub) k_fsolve<H, true, PART, BS><<<(unsigned)tiles, 256, 0, st>>>(P, a, bs);
     else k_fsolve<H, false, PART, BS><<<(unsigned)tiles, 256, 0, st>>>(P, a, bs);
+    }
     MPBP_HIP(hipGetLastError());
     return MPBP_OK;
 }

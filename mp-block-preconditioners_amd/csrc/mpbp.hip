@@ -2544,7 +2544,7 @@ struct XInit {         // staged value = the first inner iterate: c2 * (b[i] / d
 // (solve.py:274) reads one pressure field (8 B per cell, cached neighbours) instead of W's four (32 B per cell),
 // and W is never written.  One GPU (whole-grid layouts).
 struct BNone {
-    static constexpr bool on = false, part = false;
+    static constexpr bool on = false, part = false, resid = false;
     struct Q {};
     __device__ Q load(int, int, int) const { return {}; }
     template <class TA>
@@ -2553,7 +2553,7 @@ struct BNone {
 // PART: x_p in a row partition's ghost layout (L owned rows, h ghost rows each side); else the whole grid.
 template <bool PART>
 struct GxBT {
-    static constexpr bool on = true, part = PART;
+    static constexpr bool on = true, part = PART, resid = false;
     const double* __restrict__ xp;
     double d_p, inv, minv;
     int n;
@@ -2595,6 +2595,14 @@ struct GxBT {
 };
 using GxB = GxBT<false>;
 using GxBPart = GxBT<true>;
+// GxR: b = z - G x_p, the right-hand side of the upper block form's one F solve (u = F^-1 (v_u - G x_p),
+// mpbp_schur_plan.form): GxB's row of G x_p (b_at: the same products in the same periodic order), then the one
+// subtraction EpiResid makes of it -- the bits of the G launch in MPBP_SPMV_RESID mode, W never stored.  The whole-solve
+// launches only (k_fsolve_w, k_fsolve): they stage x_p as for GxB and load z per owned cell where BNone loads b.
+struct GxR : GxBT<false> {
+    static constexpr bool resid = true;
+    const double* __restrict__ z;
+};
 
 // Row of tile values held between its loads and its LDS store: every lane's main column (xa, ta; tile columns
 // c0-1 .. c0+254) and (lanes 0, 1) the halo columns c0+255, c0+256 (h0, t0).  (Holding the halo columns in SGPRs

@@ -241,6 +241,13 @@ extern "C" int mpbp_schur_apply(const mpbp_schur_plan* p, const double* v, doubl
     for (int i = 0; i < 7; ++i)
         if (!p->wp[i]) return set_error(MPBP_ERR_ARG, "schur_apply: missing pressure workspace");
     if (!p->wu_owned || !p->diag_F || !p->diag_P) return set_error(MPBP_ERR_ARG, "schur_apply: missing operands");
+    const int32_t form = p->form;
+    if (form != MPBP_FORM_FULL && form != MPBP_FORM_UPPER && form != MPBP_FORM_LOWER && form != MPBP_FORM_DIAGONAL)
+        return set_error(MPBP_ERR_ARG, "schur_apply: unknown block form %d (MPBP_FORM_*)", form);
+    if (form != MPBP_FORM_FULL && p->halo)
+        return set_error(MPBP_ERR_ARG, "schur_apply: the upper, lower and diagonal block forms are one-GPU only");
+    const bool f_first = form != MPBP_FORM_UPPER;                           // F^-1 v_u comes first ...
+    const bool d_rhs = form == MPBP_FORM_FULL || form == MPBP_FORM_LOWER;   // ... and D of it joins the pressure rhs
     if (int rc = check_opts(p->opts, "schur_apply")) return rc;
     const OptsScope scope(p->opts);
     const Ctx c{p, as_stream(stream)};
@@ -267,7 +274,8 @@ extern "C" int mpbp_schur_apply(const mpbp_schur_plan* p, const double* v, doubl
     const double* v_p = v + p->nu;
     double* out_u = out;
     double* out_p = out + p->nu;
-    double *Y = p->wu[0], *U0 = p->wu[1], *U1 = p->wu[2], *Ud = p->wu[3], *W = p->wu_owned;
+    // F^-1 v_u: the full form keeps it in Y for step 7; the lower and diagonal forms return it
+    double *Y = form == MPBP_FORM_FULL ? p->wu[0] : out_u, *U0 = p->wu[1], *U1 = p->wu[2], *Ud = p->wu[3], *W = p->wu_owned;
     double *Prhs = p->wp[0], *Pxa = p->wp[1], *Pxb = p->wp[2], *Pxp = p->wp[3];
     double *P0 = p->wp[4], *P1 = p->wp[5], *Pd = p->wp[6];
     int rc;
@@ -281,8 +289,16 @@ extern "C" int mpbp_schur_apply(const mpbp_schur_plan* p, const double* v, doubl
     double pc1[64] = {}, pc2[64] = {};
     if (px0) cheb_coeffs(p->inner_P.lmin, p->inner_P.lmax, p->inner_P.sweeps, pc1, pc2);
     // 1. Finv_v = F_inv @ v[:F.shape[1]]                                   solve.py:258
-    rc = inner_solve(c, MPBP_VEC_VELOCITY, F, p->diag_F, p->inner_F, p->nu, v_u, Y, nullptr, U0, U1, Ud, true);
-    if (rc) return rc;
+    if (f_first) {
+        rc = inner_solve(c, MPBP_VEC_VELOCITY, F, p->diag_F, p->inner_F, p->nu, v_u, Y, nullptr, U0, U1, Ud, true);
+        if (rc) return rc;
+    }
+    if (!d_rhs) {
+        // upper and diagonal forms: 3. x_a = Gt_G^-1 v_p (no producer stages the solve's x0)
+        rc = gfuse ? gtg_solve_fused(p, v_p, Pxa, c.st)
+                   : inner_solve(c, MPBP_VEC_PRESSURE, P, p->diag_P, p->inner_P, p->np, v_p, Pxa, nullptr, P0, P1, Pd, false);
+        if (rc) return rc;
+    } else
     // 2.+3. fused: the first Gt_G solve builds rhs = D Finv_v + v_p itself          solve.py:259, 265
     if (gfuse && KO().gtg_drhs && p->pg_stencil && !px0) {
         rc = gtg_solve_fused(p, nullptr, Pxa, c.st, nullptr, nullptr, GtgD{Y, v_p});
@@ -330,6 +346,20 @@ extern "C" int mpbp_schur_apply(const mpbp_schur_plan* p, const double* v, doubl
     if (rc) return rc;
     if (Pxp != out_p)
         MPBP_HIP(hipMemcpyAsync(out_p, Pxp, sizeof(double) * (size_t)p->np, hipMemcpyDeviceToDevice, c.st));
+    if (form == MPBP_FORM_LOWER || form == MPBP_FORM_DIAGONAL) return MPBP_OK;   // u = F^-1 v_u is in place
+    if (form == MPBP_FORM_UPPER) {
+        // u = F^-1 (v_u - G x_p): one whole-solve launch that builds the right-hand side per cell (GxR), or
+        if (p->fuse_g) {
+            bool taken = false;
+            rc = f_solve_gr(c, Pxp, v_u, p->inner_F, out_u, true, &taken);
+            if (rc || taken) return rc;
+        }
+        // W = v_u - G x_p by the G operator, then the F solve
+        rc = two_phase(c, MPBP_VEC_PRESSURE, Pxp, G,
+                       [&](const OpRef& o) { return op_spmv(o, MPBP_SPMV_RESID, Pxp, v_u, W, c.st); });
+        if (rc) return rc;
+        return inner_solve(c, MPBP_VEC_VELOCITY, F, p->diag_F, p->inner_F, p->nu, W, out_u, nullptr, U0, U1, Ud, true);
+    }
     // 6.+7. fused: the second F solve recomputes G x_p in its sweeps (one GPU, matrix-free F and G, Chebyshev F)
     if (p->fuse_g && !p->halo && p->f_stencil && p->pg_stencil && p->inner_F.kind == MPBP_INNER_CHEBYSHEV &&
         p->inner_F.sweeps >= 2)

@@ -311,4 +311,29 @@ int f_solve_gx(const Ctx& c, const double* xp, const mpbp_inner_solver& in, doub
     return MPBP_OK;
 }
 
+// The upper block form's u = F^-1 (v_u - G x_p) (mpbp_schur_plan.form) as ONE whole-solve launch whose right-hand side
+// is built per cell from v_u and x_p (GxR): no G launch, W never stored, the bits of the G launch in MPBP_SPMV_RESID
+// mode followed by inner_solve.  One GPU, matrix-free F and G, fast numerics, Chebyshev F of 3 or 4 sweeps on a grid
+// the launch takes (fsolve_ok); *taken says whether it ran -- otherwise nothing was launched and the caller runs the pair.
+int f_solve_gr(const Ctx& c, const double* xp, const double* v_u, const mpbp_inner_solver& in, double* dst, bool profile,
+               bool* taken) {
+    const mpbp_schur_plan* p = c.p;
+    const int K = in.sweeps;
+    *taken = false;
+    if (p->halo || !p->f_stencil || !p->pg_stencil || in.kind != MPBP_INNER_CHEBYSHEV || !(in.lmax > in.lmin) ||
+        !(in.lmin >= 0.0) || !f_pair_ok(p) || !KO().f_solve || !fsolve_ok(K, p->f_prm.n))
+        return MPBP_OK;
+    double c1[64] = {}, c2[64] = {};
+    cheb_coeffs(in.lmin, in.lmax, K, c1, c2);
+    FStencilDev P;
+    int rc = make_fstencil(&p->f_prm, p->f_cell, p->f_uface, p->f_vface, nullptr, &P);
+    if (rc) return rc;
+    PGDev G;
+    rc = make_pgstencil(&p->f_prm, p->f_cell, nullptr, &G);
+    if (rc) return rc;
+    const GxR bs{{xp, G.d_p, G.inv, G.minv, G.n}, v_u};
+    *taken = true;
+    return profiled(p, profile, c.st, [&] { return launch_fsolve(P, K, c1, c2, nullptr, nullptr, dst, c.st, bs); });
+}
+
 }  // namespace

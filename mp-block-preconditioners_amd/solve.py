@@ -113,6 +113,19 @@ def _check_numerics(numerics: str) -> str:
     return numerics
 
 
+FORMS = ("full", "upper", "lower", "diagonal")
+
+
+def _check_form(form: str) -> str:
+    """Which block form of A = [[F, G], [-D, 0]] the apply inverts (mpbp_schur_plan.form), S~^-1 = Gt_G^-1 Gt_F_G
+    Gt_G^-1 throughout: 'full' the block-LU inverse approx_schur_op (solve.py:257-277, two F solves); 'upper'
+    [[F, G], [0, S]] (solve.py:191-196's matrix: x_p = S~^-1 v_p, u = F^-1 (v_u - G x_p)); 'lower' [[F, 0], [-D, S]]
+    (u = F^-1 v_u, x_p = S~^-1 (D u + v_p)); 'diagonal' [[F, 0], [0, S]].  The three new forms solve with F once."""
+    if form not in FORMS:
+        raise ValueError(f"form must be one of {FORMS}")
+    return form
+
+
 def _device_csr(M, device):
     return M if isinstance(M, DeviceCSR) else DeviceCSR.from_scipy(M, device)
 
@@ -268,7 +281,9 @@ def _capture(pc, v: torch.Tensor, out: torch.Tensor, capture_error_mode: str = "
 
 
 class ApproxSchurPreconditioner(PlanProfiling, spla.LinearOperator):
-    """M^-1 of the block upper-triangular approximate-commutator preconditioner (solve.py:257-277).
+    """M^-1 of the approximate-commutator block preconditioner: by default (``form="full"``) the block-LU inverse
+    approx_schur_op (solve.py:257-277); ``form`` "upper", "lower" or "diagonal" the block-triangular and block-diagonal
+    forms built from the same inner solves and operators (one F solve per apply instead of two; see _check_form).
 
     ``apply(v, out)`` works on CUDA tensors and is graph-capturable; ``matvec`` (the scipy
     LinearOperator surface) copies a host vector in and out around the same apply.
@@ -277,9 +292,10 @@ class ApproxSchurPreconditioner(PlanProfiling, spla.LinearOperator):
     def __init__(self, F, D, G, GtG=None, GtFG=None, inner_F: InnerSolver | None = None,
                  inner_P: InnerSolver | None = None, device=None, layout: str = "sell", f_mode: str = "auto",
                  pg_mode: str = "auto", q_mode: str = "auto", fuse_g: bool = True, numerics: str = "exact",
-                 kernel_opts: dict | None = None):
+                 kernel_opts: dict | None = None, form: str = "full"):
         dev = torch.device(device or (F.device if isinstance(F, DeviceCSR) else "cuda"))
         self.numerics = _check_numerics(numerics)
+        self.form = _check_form(form)
         # this preconditioner's kernel choices (mpbp_kernel_opts): the process defaults now, with `kernel_opts`
         # overrides -- later mpbp_set_* calls and other preconditioners' choices do not affect it
         self.kernel_opts = _lib.kernel_opts(kernel_opts)
@@ -352,8 +368,11 @@ class ApproxSchurPreconditioner(PlanProfiling, spla.LinearOperator):
             if not a[0] <= 1e-14 * a[1]:
                 self.kernel_opts.q13_sym = 0
         # the second F solve recomputes its right-hand side G x_p inside its sweeps (no G launch, W never stored)
-        # when F and G are both matrix-free and F's inner solve is Chebyshev with >= 2 sweeps; same bits
-        self.fuse_g = bool(fuse_g and self.f_stencil is not None and self.pg_stencil is not None
+        # when F and G are both matrix-free and F's inner solve is Chebyshev with >= 2 sweeps; same bits.  The upper
+        # form's one F solve likewise builds v_u - G x_p per cell (the whole-solve launch; else G runs apart); the
+        # lower and diagonal forms never apply G
+        self.fuse_g = bool(fuse_g and self.form in ("full", "upper") and self.f_stencil is not None
+                           and self.pg_stencil is not None
                            and self.inner_F.kind == "chebyshev" and self.inner_F.sweeps >= 2)
         self._plan = self._make_plan()
         super().__init__(dtype=np.float64, shape=(nu + np_, nu + np_))
@@ -404,6 +423,7 @@ class ApproxSchurPreconditioner(PlanProfiling, spla.LinearOperator):
         p.fuse_g = 1 if self.fuse_g else 0
         p.f_numerics = _lib.NUMERICS_FAST if self.numerics == "fast" else _lib.NUMERICS_EXACT
         p.opts = ctypes.pointer(self.kernel_opts)
+        p.form = FORMS.index(self.form)   # MPBP_FORM_*
         return p
 
     # -- a time step: new values, same grid ---------------------------------------------------------------
@@ -1004,16 +1024,17 @@ def print_true_res_norm(A, b_vec):
 
 
 def solve_with_approx_schur_pc(n, xi, etan, etas, c, d, b_vec, u_vec, inner_F=None, inner_P=None,
-                               tol=1e-8, maxiter=150, verbose=True, matrix_free_A=False):
+                               tol=1e-8, maxiter=150, verbose=True, matrix_free_A=False, form="full"):
     """solve.py:240-286: FGMRES on A with the approximate-commutator preconditioner.
 
+    form: the preconditioner's block form (ApproxSchurPreconditioner; "full" is the reference's approx_schur_op).
     matrix_free_A: A is never assembled, FGMRES applies it through the StokesOperator (same bits, n >= 3).
     Returns (u_approx, info, residual history) with u_approx a host array.
     """
     from .utils import print_norms
     bp = MultiphaseBlockPreconditioner(n, xi, etan, etas)
     A, _, F, D, G = bp.get_big_A_matrix(c=c, d_u=d, matrix_free_A=matrix_free_A)
-    pc = ApproxSchurPreconditioner(F, D, G, inner_F=inner_F, inner_P=inner_P)
+    pc = ApproxSchurPreconditioner(F, D, G, inner_F=inner_F, inner_P=inner_P, form=form)
     b = torch.from_numpy(np.ascontiguousarray(b_vec, dtype=np.float64)).to(pc.device)
     hist = []
     x, info = fgmres(A, b, M=pc, tol=tol, maxiter=maxiter,

@@ -36,8 +36,10 @@ import torch
 from . import _lib
 from ._lib import check, lib, ptr, stream_handle
 from .csr import DeviceCSR, spgemm
-from .preconditioner import PGStencil
-from .solve import PlanProfiling, _capture, _pg_stencil
+from .mg import FIELDS_PRESSURE, FIELDS_VELOCITY, level_sizes
+from .preconditioner import MultiphaseBlockPreconditioner, PGStencil
+from .solve import (InnerSolver, PlanProfiling, _capture, _check_f_mode, _check_layout, _check_numerics, _check_pg_mode,
+                    _f_stencil, _fill_plan, _pg_stencil)
 
 N_VEL_FIELDS = 4
 N_P_FIELDS = 1
@@ -883,90 +885,66 @@ def _phase_clock(out: dict):
     return stamp
 
 
-class DistributedMatrix:
-    """A row-partitioned operator of the MAC-grid system: the operator matvec b = A u of apply.py:72 and the FGMRES
-    operator of solve.py:285 (A @ xk, solve.py:166) over the ranks of `group`, one per GPU.
+def _check_halo(halo: str) -> str:
+    if halo not in ("auto", "rccl", "torch"):
+        raise ValueError("halo must be 'auto', 'rccl' or 'torch'")
+    return halo
 
-    Rank k holds the rows of grid rows [r0, r1) of every one of `nfields` stacked n x n fields (A: the 5 fields
-    [u_n, v_n, u_s, v_s, p]), columns renumbered into the owned + ghost ("ext") layout (DeviceCSR.extract keeps each
-    row's entry order: every local row sum is the global one, bit for bit).  apply(x) takes and returns the rank's
-    owned entries: x is copied into the ext buffer, the ghost rows are exchanged (RCCL neighbour point-to-point over
-    xGMI -- overlap=True: on the halo's own high-priority stream, forked before and joined after the interior rows'
-    SpMV, so the transfer overlaps it), the interior rows (no ghost column) run on the CSR kernel meanwhile and the
-    boundary rows after the join.  With the gloo backend the ghosts are host-staged (HaloExchanger)."""
 
-    def __init__(self, M: DeviceCSR, n: int, nfields: int, group=None, halo: str = "auto", overlap: bool = True,
-                 self_halo: bool = False, owned_rows: bool = False):
-        """M: the global operator, or (owned_rows=True) just this rank's rows of it, in owned order, with global
-        columns (MultiphaseBlockPreconditioner.assemble_rows: rank-local setup)."""
-        dist, world, rank, backend = _dist_info(group)
-        dev = M.device
-        N_all = nfields * n * n
-        self.part = part = RowPartition(n, world, rank, ghosts=bool(self_halo))
-        if M.shape != ((part.n_owned(nfields) if owned_rows else N_all), N_all):
-            raise ValueError(f"operator {M.shape} is not {'this rank' + chr(39) + 's rows of ' if owned_rows else ''}"
-                             f"{nfields} fields of a {n} x {n} grid")
+class _PartitionedOperator:
+    """What the row-partitioned operators of the system share: the partition, the owned + ghost ("ext") input buffer
+    ``xe`` with its ghost-row exchange, and the schedule of apply(x) on the rank's owned entries -- x copied into xe,
+    the exchange begun, the rows that read no ghost launched, the exchange ended, the boundary rows launched.  The
+    exchange is RCCL neighbour point-to-point over xGMI on a communicator of this object's own (its eager exchanges --
+    overlap=True: on the halo object's high-priority side stream, forked before and joined after the interior launch
+    -- are never mixed with a preconditioner's in-order ones inside a replayed graph on one communicator), or with the
+    gloo backend the host-staged HaloExchanger.  A subclass supplies _whole (the unpartitioned apply), _interior and
+    _boundary."""
+
+    def __init__(self, n: int, nfields: int, group, halo: str, self_halo: bool):
+        _check_halo(halo)
+        _, world, rank, backend = _dist_info(group)
         self.nfields = nfields
-        self.partitioned = part.ghosts
+        self.part = RowPartition(n, world, rank, ghosts=bool(self_halo))
+        self.partitioned = self.part.ghosts
         self.halo_impl = halo if halo != "auto" else ("rccl" if backend == "nccl" else "torch")
-        rows = torch.from_numpy(part.owned_rows(nfields).astype(np.int32)).to(dev)
-        if owned_rows:
-            full, rows = M, torch.arange(M.shape[0], dtype=torch.int32, device=dev)
-        else:
-            full = M.extract(rows, torch.arange(M.shape[1], dtype=torch.int32, device=dev), M.shape[1])
-        self.h = max(1, ghost_depth(full.col_idx, n, part.r0, part.L) if world > 1 else 1)
-        del full
-        self.n_own = part.n_owned(nfields)
-        self.n_ext = part.n_ext(nfields, self.h)
-        self.shape = (self.n_own, self.n_own)
-        if owned_rows and not self.partitioned:
-            raise ValueError("owned_rows=True needs a row partition")
-        self.A = M.extract(rows, torch.from_numpy(part.colmap(nfields, self.h)).to(dev), self.n_ext) \
-            if self.partitioned else M
-        if self.partitioned and world > 1:
-            inner, bnd = boundary_ranges(self.A.row_ptr, self.A.col_idx, self.n_own)
-        elif self.partitioned:   # one rank exchanging with itself: every row with a wrapped neighbour reads ghosts
-            inner, bnd = boundary_ranges(self.A.row_ptr, self.A.col_idx, self.n_own)
-        else:
-            inner, bnd = [(0, self.n_own)], []
-        self.blk_in = self.A.plan_blocks(rows=inner) if inner else None
-        self.blk_bd = self.A.plan_blocks(rows=bnd) if bnd else None
-        self.xe = torch.zeros(self.n_ext, dtype=torch.float64, device=dev)
-        self._rccl = self._ex = None
-        if self.partitioned:
-            if self.halo_impl == "rccl":
-                # its own communicator: its exchanges run eagerly on the halo object's side stream (overlap), the
-                # preconditioner's in order on the caller's stream inside a replayed graph -- the two are never mixed
-                # on one communicator
-                self._rccl = RcclHalo(part, 1, 1, group, overlap=False, share=False)
-                self.kind = self._rccl.add_kind(part, nfields, self.h, overlap=overlap)
-            else:
-                self._ex = HaloExchanger(part, nfields, self.h, dev, group)
+        self._rccl = self._ex = self.xe = None
 
-    @property
-    def device(self):
-        return self.xe.device
+    def _open_halo(self, h: int, device, group, overlap: bool):
+        """The sizes at ghost depth h and, under a partition, xe and its exchange."""
+        part, nf = self.part, self.nfields
+        self.h = h
+        self.n_own, self.n_ext = part.n_owned(nf), part.n_ext(nf, h)
+        self.shape = (self.n_own, self.n_own)
+        if not self.partitioned:
+            return
+        self.xe = torch.zeros(self.n_ext, dtype=torch.float64, device=device)
+        if self.halo_impl == "rccl":
+            self._rccl = RcclHalo(part, 1, 1, group, overlap=False, share=False)
+            self.kind = self._rccl.add_kind(part, nf, h, overlap=overlap)
+        else:
+            self._ex = HaloExchanger(part, nf, h, device, group)
+
+    def _exchange(self, phase):
+        if self._rccl is not None:
+            lib().mpbp_halo_exchange(self._rccl.handle, self.kind, ptr(self.xe), phase, stream_handle())
+        elif phase == _lib.HALO_BEGIN:
+            self._ex.begin(self.xe)
+        else:
+            self._ex.end(self.xe)
 
     def apply(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         assert x.is_cuda and x.dtype == torch.float64 and x.numel() == self.n_own
         if out is None:
             out = torch.empty(self.n_own, dtype=torch.float64, device=x.device)
         if not self.partitioned:
-            return self.A.matvec(x, out=out)
+            return self._whole(x, out)
+        assert out.is_cuda and out.dtype == torch.float64 and out.numel() == self.n_own
         self.xe[: self.n_own].copy_(x)
-        st = stream_handle()
-        if self._rccl is not None:
-            lib().mpbp_halo_exchange(self._rccl.handle, self.kind, ptr(self.xe), _lib.HALO_BEGIN, st)
-        else:
-            self._ex.begin(self.xe)
-        if self.blk_in is not None:
-            self.A.matvec(self.xe, out=out, blocks=self.blk_in)
-        if self._rccl is not None:
-            lib().mpbp_halo_exchange(self._rccl.handle, self.kind, ptr(self.xe), _lib.HALO_END, st)
-        else:
-            self._ex.end(self.xe)
-        if self.blk_bd is not None:
-            self.A.matvec(self.xe, out=out, blocks=self.blk_bd)
+        self._exchange(_lib.HALO_BEGIN)
+        self._interior(out)
+        self._exchange(_lib.HALO_END)
+        self._boundary(out)
         if self._rccl is not None:
             self._rccl.check()
         return out
@@ -982,7 +960,61 @@ class DistributedMatrix:
         return self.part.owned_rows(self.nfields)
 
 
-class DistributedStokesOperator:
+class DistributedMatrix(_PartitionedOperator):
+    """A row-partitioned operator of the MAC-grid system: the operator matvec b = A u of apply.py:72 and the FGMRES
+    operator of solve.py:285 (A @ xk, solve.py:166) over the ranks of `group`, one per GPU.
+
+    Rank k holds the rows of grid rows [r0, r1) of every one of `nfields` stacked n x n fields (A: the 5 fields
+    [u_n, v_n, u_s, v_s, p]), columns renumbered into the owned + ghost ("ext") layout (DeviceCSR.extract keeps each
+    row's entry order: every local row sum is the global one, bit for bit).  apply(x) takes and returns the rank's
+    owned entries (_PartitionedOperator's schedule): the interior rows (no ghost column) run on the CSR kernel while
+    the ghost rows are exchanged, the boundary rows after."""
+
+    def __init__(self, M: DeviceCSR, n: int, nfields: int, group=None, halo: str = "auto", overlap: bool = True,
+                 self_halo: bool = False, owned_rows: bool = False):
+        """M: the global operator, or (owned_rows=True) just this rank's rows of it, in owned order, with global
+        columns (MultiphaseBlockPreconditioner.assemble_rows: rank-local setup)."""
+        super().__init__(n, nfields, group, halo, self_halo)
+        part, dev = self.part, M.device
+        N_all = nfields * n * n
+        if M.shape != ((part.n_owned(nfields) if owned_rows else N_all), N_all):
+            raise ValueError(f"operator {M.shape} is not {'this rank' + chr(39) + 's rows of ' if owned_rows else ''}"
+                             f"{nfields} fields of a {n} x {n} grid")
+        rows = torch.from_numpy(part.owned_rows(nfields).astype(np.int32)).to(dev)
+        if owned_rows:
+            full, rows = M, torch.arange(M.shape[0], dtype=torch.int32, device=dev)
+        else:
+            full = M.extract(rows, torch.arange(M.shape[1], dtype=torch.int32, device=dev), M.shape[1])
+        h = max(1, ghost_depth(full.col_idx, n, part.r0, part.L) if part.world > 1 else 1)
+        del full
+        if owned_rows and not self.partitioned:
+            raise ValueError("owned_rows=True needs a row partition")
+        self._open_halo(h, dev, group, overlap)
+        self.A = M.extract(rows, torch.from_numpy(part.colmap(nfields, h)).to(dev), self.n_ext) \
+            if self.partitioned else M
+        # (one rank exchanging with itself: every row with a wrapped neighbour reads ghosts)
+        inner, bnd = boundary_ranges(self.A.row_ptr, self.A.col_idx, self.n_own) if self.partitioned else \
+            ([(0, self.n_own)], [])
+        self.blk_in = self.A.plan_blocks(rows=inner) if inner else None
+        self.blk_bd = self.A.plan_blocks(rows=bnd) if bnd else None
+
+    @property
+    def device(self):
+        return self.A.device
+
+    def _whole(self, x, out):
+        return self.A.matvec(x, out=out)
+
+    def _interior(self, out):
+        if self.blk_in is not None:
+            self.A.matvec(self.xe, out=out, blocks=self.blk_in)
+
+    def _boundary(self, out):
+        if self.blk_bd is not None:
+            self.A.matvec(self.xe, out=out, blocks=self.blk_bd)
+
+
+class DistributedStokesOperator(_PartitionedOperator):
     """The row-partitioned system matrix applied matrix-free: DistributedMatrix's surface and schedule with every owned
     row of ``A x`` recomputed from the thn tables (mpbp_stokes_apply_part) -- no row of A assembled, extracted,
     renumbered or planned on any rank.
@@ -1001,37 +1033,18 @@ class DistributedStokesOperator:
     Needs n >= 3.  Every rank holds the three GLOBAL thn tables (3 n^2 doubles: 100 MB at 2048^2) -- the tables are
     not partitioned."""
 
-    nfields = 5
-    h = 1
-
     def __init__(self, op, group=None, halo: str = "auto", overlap: bool = True, self_halo: bool = False):
         from .preconditioner import StokesOperator
         if not isinstance(op, StokesOperator):
             raise TypeError("DistributedStokesOperator needs a StokesOperator (MultiphaseBlockPreconditioner.stokes_operator)")
-        if halo not in ("auto", "rccl", "torch"):
-            raise ValueError("halo must be 'auto', 'rccl' or 'torch'")
-        dist, world, rank, backend = _dist_info(group)
         n = int(op.prm.n)
         if n < 3:
             raise ValueError("DistributedStokesOperator needs n >= 3")
+        super().__init__(n, 5, group, halo, self_halo)
         self.op = op
-        self.part = part = RowPartition(n, world, rank, ghosts=bool(self_halo))
-        self.partitioned = part.ghosts
-        self.halo_impl = halo if halo != "auto" else ("rccl" if backend == "nccl" else "torch")
-        self.n_own = part.n_owned(5)
-        self.n_ext = part.n_ext(5, self.h)
-        self.shape = (self.n_own, self.n_own)
-        self._rccl = self._ex = self.xe = None
+        self._open_halo(1, op.device, group, overlap)
         if self.partitioned:
-            self.xe = torch.zeros(self.n_ext, dtype=torch.float64, device=op.device)
-            self._parts = tuple(_lib.RowPart(part.r0, part.L, self.h, which, 0, 0) for which in (0, 1, 2))
-            if self.halo_impl == "rccl":
-                # its own communicator, as DistributedMatrix: eager exchanges on the halo object's side stream are never
-                # mixed with the preconditioner's in-order ones on one communicator
-                self._rccl = RcclHalo(part, 1, 1, group, overlap=False, share=False)
-                self.kind = self._rccl.add_kind(part, 5, self.h, overlap=overlap)
-            else:
-                self._ex = HaloExchanger(part, 5, self.h, op.device, group)
+            self._parts = tuple(_lib.RowPart(self.part.r0, self.part.L, self.h, which, 0, 0) for which in (0, 1, 2))
 
     @property
     def device(self):
@@ -1048,38 +1061,14 @@ class DistributedStokesOperator:
                                            ctypes.byref(self._parts[which]), flags, ptr(self.xe), ptr(z), ptr(out),
                                            stream_handle()))
 
-    def apply(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-        assert x.is_cuda and x.dtype == torch.float64 and x.numel() == self.n_own
-        if out is None:
-            out = torch.empty(self.n_own, dtype=torch.float64, device=x.device)
-        if not self.partitioned:
-            return self.op.matvec(x, out=out)
-        assert out.is_cuda and out.dtype == torch.float64 and out.numel() == self.n_own
-        self.xe[: self.n_own].copy_(x)
-        st = stream_handle()
-        if self._rccl is not None:
-            lib().mpbp_halo_exchange(self._rccl.handle, self.kind, ptr(self.xe), _lib.HALO_BEGIN, st)
-        else:
-            self._ex.begin(self.xe)
+    def _whole(self, x, out):
+        return self.op.matvec(x, out=out)
+
+    def _interior(self, out):
         self._launch(1, out)          # rows 1 .. L-2: no ghost row read (nothing launched when L <= 2)
-        if self._rccl is not None:
-            lib().mpbp_halo_exchange(self._rccl.handle, self.kind, ptr(self.xe), _lib.HALO_END, st)
-        else:
-            self._ex.end(self.xe)
+
+    def _boundary(self, out):
         self._launch(2, out)          # the first and last owned grid rows
-        if self._rccl is not None:
-            self._rccl.check()
-        return out
-
-    matvec = apply
-
-    def close(self):
-        if self._rccl is not None:
-            self._rccl.close()
-            self._rccl = None
-
-    def local_to_global_rows(self):
-        return self.part.owned_rows(5)
 
     def __repr__(self):
         return (f"DistributedStokesOperator(n={self.part.n}, rows=[{self.part.r0}, {self.part.r1}), "
@@ -1121,12 +1110,197 @@ def _q13_block(Q: DeviceCSR, n: int, part, group, red_dev):
     return n, vals, bool(a[0] <= 1e-14 * a[1])
 
 
+# the apply's five operators: plan key -> (attribute, row kind, column kind); "u": the four velocity fields, "p": pressure
+_OPS = {"F": ("F", "u", "u"), "D": ("D", "p", "u"), "G": ("G", "u", "p"), "P": ("GtG", "p", "p"), "Q": ("GtFG", "p", "p")}
+
+
+class _RowSource:
+    """Where a rank's rows of level 0 come from during the partitioned setup.  Two sources, one surface (as
+    LocalHierarchy / _GlobalLevels one level down); DistributedSchurPreconditioner picks one and is written once
+    against it:
+
+        op[key]                      F / D / G / P (Gt_G) / Q (Gt_F_G), global columns, stencils attached
+        q13_rows()                   fast numerics: Gt_F_G's grid rows r0 - 2 .. r0 + L - 1 for _q13_block, else None
+        resolve(ik, key)             the inner solver with its Chebyshev interval from the GLOBAL operator's bound
+        reach(key)                   the halo reach of the operator on the owned rows
+        hierarchy(ik, key, fields)   what PartitionedMultigrid splits: the multigrid levels for one inner solver
+        ext_diagonal(key, rows)      the operator's diagonal on owned + ghost rows (the CA schedule)
+        owned_ext(key, cmap, ncols)  the owned rows with their columns in the ext layout
+
+    A source holds every setup-only operator and assembly object; dropping it frees them."""
+
+    def __init__(self, bp, part: RowPartition, *, akw: dict, inners, want_q13: bool, group, red_dev, mg_limits, stamp):
+        self.bp, self.part, self.akw, self.group, self.red_dev = bp, part, akw, group, red_dev
+        self.mg_limits, self.stamp = mg_limits, stamp
+        self.n, self.dev = part.n, bp.device
+        self.rows = {"u": torch.from_numpy(part.owned_rows(N_VEL_FIELDS).astype(np.int32)).to(self.dev),
+                     "p": torch.from_numpy(part.owned_rows(N_P_FIELDS).astype(np.int32)).to(self.dev)}
+        self._q_rows = None
+        self.op = dict(zip("FDGPQ", self._assemble(inners, want_q13)))
+
+    def _rows_of(self, key):
+        return self.rows[_OPS[key][1]]
+
+    def q13_rows(self):
+        rows, self._q_rows = self._q_rows, None   # handed over: dead once the diamond is built
+        return rows
+
+
+class _GlobalOperators(_RowSource):
+    """Every rank assembles the global F, D, G and forms the global products and multigrid hierarchies (setup memory
+    and work O(N) on every rank), then keeps its rows: the only source on one rank, ``local_products=False`` on more."""
+
+    def _assemble(self, inners, want_q13):
+        part, n = self.part, self.n
+        # (the preconditioner reads F, D and G alone: A's own CSR is not assembled to be dropped)
+        _, _, F, D, G = self.bp.get_big_A_matrix(matrix_free_A=n >= 3, **self.akw)
+        self.stamp("assemble_global")
+        GtG, GtFG = self.bp.commutator_products(F, D, G)
+        self.stamp("commutator_products")
+        if want_q13:
+            blk = np.concatenate([((part.r0 + k) % n) * n + np.arange(n) for k in range(-2, part.L)]).astype(np.int32)
+            self._q_rows = self._rows(GtFG, torch.from_numpy(blk).to(self.dev))
+        return F, D, G, GtG, GtFG
+
+    def _rows(self, M, rows):
+        return M.extract(rows, torch.arange(M.shape[1], dtype=torch.int32, device=self.dev), M.shape[1])
+
+    def resolve(self, ik, key):
+        return ik.resolve(self.op[key], self.op[key].diagonal())
+
+    def reach(self, key):
+        sub = self._rows(self.op[key], self._rows_of(key))
+        return halo_reach(sub.row_ptr, sub.col_idx, self._rows_of(key), self.n)
+
+    def hierarchy(self, ik, key, fields):
+        return ik.multigrid(self.op[key], self.n, fields, self.op[key].diagonal())
+
+    def ext_diagonal(self, key, rows):
+        return self.op[key].diagonal()[rows.long()].contiguous()
+
+    def owned_ext(self, key, colmap, ncols):
+        return self.op[key].extract(self._rows_of(key), colmap, ncols)
+
+
+class _RankLocalRows(_RowSource):
+    """Rank-local setup (preconditioner.py:299-341 row by row): F, D, G assembled on this rank's rows only
+    (mpbp_stokes_*_rows, the global assembly's rows bit for bit) and only this rank's pressure rows of Gt_G and Gt_F_G
+    (a product's row depends on that row of D alone: the same bits as the global product's row, for a 1 / world share
+    of the SpGEMM work); setup memory and work O(N / world + ghosts) instead of O(N).  Needs world > 1."""
+
+    def _assemble(self, inners, want_q13):
+        bp, part, n, dev, akw = self.bp, self.part, self.n, self.dev, self.akw
+        st_F, st_D, st_G = bp.stencils(**akw)
+        F = bp.assemble_rows(_lib.OP_F, self.rows["u"], **akw)
+        D = bp.assemble_rows(_lib.OP_D, self.rows["p"], **akw)
+        G = bp.assemble_rows(_lib.OP_G, self.rows["u"], **akw)
+        F.stencil, D.stencil, G.stencil = st_F, st_D, st_G
+        self.stamp("assemble_owned_rows")
+        # the products' right operands on the velocity rows a product row can reach -- grid rows within `sup` of the
+        # owned ones (the CA schedule's ghost depths included) -- in global row numbering
+        sup = min(n, sum(k.sweeps if k.kind in ("jacobi", "chebyshev") else 1 for k in inners) + 2)
+        grid_rows = np.unique(np.arange(part.r0 - sup, part.r1 + sup) % n) if part.L + 2 * sup < n else np.arange(n)
+        sup_u = np.sort(np.concatenate([f * part.N + (r * n + np.arange(n)) for f in range(N_VEL_FIELDS)
+                                        for r in grid_rows]))
+        sup_u = torch.from_numpy(sup_u.astype(np.int32)).to(dev)
+        Fs = bp.assemble_rows(_lib.OP_F, sup_u, global_shape=True, **akw)
+        self.Gs = bp.assemble_rows(_lib.OP_G, sup_u, global_shape=True, **akw)
+        self.stamp("assemble_support_rows")
+        GtG, GtFG = bp.commutator_products(Fs, D, self.Gs)   # this rank's pressure rows, global columns
+        self.stamp("commutator_products")
+        GtG.stencil = _gtg_stencil(D, G)
+        if want_q13:
+            # the two pressure grid rows above the owned block too (their products' rows, bit for bit the global
+            # product's), so the symmetric-half read has the lower slots of the first owned rows
+            self._q_rows = GtFG
+            for k in (1, 2):   # (one grid row per assembly: the wrapped rows need not ascend)
+                row = torch.from_numpy((((part.r0 - k) % n) * n + np.arange(n)).astype(np.int32)).to(dev)
+                D1 = bp.assemble_rows(_lib.OP_D, row, **akw)
+                self._q_rows = _csr_vstack(spgemm(spgemm(D1, Fs, alpha=-1.0), self.Gs, alpha=1.0), self._q_rows)
+        return F, D, G, GtG, GtFG
+
+    def resolve(self, ik, key):
+        """The Gershgorin bound is the maximum of the ranks' row bounds: the global operator's, exactly, on every rank."""
+        import torch.distributed as dist
+        M = self.op[key]
+        if ik.kind == "chebyshev" and ik.lmax is None:
+            t = torch.tensor([M.gershgorin(_row_diagonal(M, self._rows_of(key)))], dtype=torch.float64,
+                             device=self.red_dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+            ik = InnerSolver("chebyshev", ik.sweeps, ik.lmin, float(t.item()), ik.ratio)
+        return ik.resolve(M, None)
+
+    def reach(self, key):
+        return halo_reach(self.op[key].row_ptr, self.op[key].col_idx, self._rows_of(key), self.n)
+
+    def hierarchy(self, ik, key, fields):
+        """This rank's band of level 0 (mg_bands), then its Galerkin levels (LocalHierarchy): no global operator."""
+        sizes = level_sizes(self.n, ik.coarsest)
+        cap = mg_part_cap(sizes, self.part, len(fields), *self.mg_limits)
+        S = mg_bands(sizes, fields, self.part, cap, self.dev)
+        self.stamp("mg_bands")
+        A0 = self._band(key, S[0])
+        self.stamp("mg_band_level0")
+        return LocalHierarchy(A0, S, sizes, fields, self.part, self.group, pre=ik.pre, post=ik.post,
+                              cycles=int(ik.sweeps), ratio=ik.smooth_ratio, coarsest=ik.coarsest, stamp=self.stamp)
+
+    def _band(self, key, rows, G=None):
+        """Rows `rows` of F or of Gt_G = (-D) G, from those rows alone.  G: an assembled G that holds the velocity rows
+        those rows of D reach (default: assembled here on exactly them)."""
+        if key == "F":
+            return self.bp.assemble_rows(_lib.OP_F, rows, **self.akw)
+        D = self.bp.assemble_rows(_lib.OP_D, rows, **self.akw)
+        if G is None:
+            G = self.bp.assemble_rows(_lib.OP_G, torch.unique(D.col_idx), global_shape=True, **self.akw)
+        return spgemm(D, G, alpha=-1.0)
+
+    def ext_diagonal(self, key, rows):
+        return _row_diagonal(self._band(key, rows, self.Gs), rows)
+
+    def owned_ext(self, key, colmap, ncols):   # already this rank's rows, in owned order
+        M = self.op[key]
+        return M.extract(torch.arange(M.shape[0], dtype=torch.int32, device=self.dev), colmap, ncols)
+
+
+def _check_setup_args(inner_F, inner_P, halo, f_mode, pg_mode, ca, layout, numerics):
+    """Every refusal that depends on the arguments alone, before any torch.distributed call: a bad argument on one
+    rank must not leave the others waiting in a collective."""
+    for name, inner in (("inner_F", inner_F), ("inner_P", inner_P)):
+        if getattr(inner, "accel", None) is not None:
+            raise ValueError(f"{name}: Chebyshev-accelerated multigrid (accel={inner.accel!r}) is not available on "
+                             "the row-partitioned hierarchies; use accel=None here")
+        if getattr(inner, "coarsen", "even") != "even":
+            raise ValueError(f"{name}: coarsen={inner.coarsen!r} is not available under the row partition; use "
+                             'coarsen="even" here')
+    _check_halo(halo)
+    _check_f_mode(f_mode)
+    _check_pg_mode(pg_mode)
+    _check_layout(layout)
+    _check_numerics(numerics)
+    if ca not in ("auto", True, False):
+        raise ValueError("ca must be 'auto', True or False")
+    if ca is True and "mg" in (getattr(inner_F, "kind", None), getattr(inner_P, "kind", None)):
+        raise ValueError("ca=True needs Jacobi / Chebyshev inner solves (multigrid exchanges per operator)")
+
+
+def _split_pieces(M: DeviceCSR, n_own_cols: int, layout: str, split: bool):
+    """(the SELL copy or None, _fill_plan's piece) of one operator in the ext layout: its interior rows (no ghost
+    column; every row when not `split`) and its boundary rows, as SELL slices of one copy or as CSR row blocks."""
+    inner, bnd = boundary_ranges(M.row_ptr, M.col_idx, n_own_cols) if split else ([(0, M.shape[0])], [])
+    if layout == "sell":
+        S = M.to_sell(inner + bnd)
+        n_in = sum((b - a + 63) // 64 for a, b in inner)
+        return S, ((None, None), (S.sub(0, n_in), S.sub(n_in, S.nslices - n_in)))
+    return None, ((M.plan_blocks(rows=inner) if inner else None, M.plan_blocks(rows=bnd) if bnd else None), (None, None))
+
+
 class DistributedSchurPreconditioner(PlanProfiling):
     """The approximate-commutator apply over a row partition of the grid (one rank per GPU).
 
-    Every rank assembles the global operators in its own HBM (setup only), keeps its rows with
-    columns renumbered into the owned+ghost layout, and runs ``mpbp_schur_apply`` with halo
-    callbacks; v and the result hold the rank's owned unknowns [u_n, v_n, u_s, v_s, p] rows r0..r1.
+    Every rank forms its rows of the operators (setup only: from its own rows, or from the global operators in its own
+    HBM -- ``local_products``), keeps them with columns renumbered into the owned+ghost layout, and runs
+    ``mpbp_schur_apply`` with halo callbacks; v and the result hold the rank's owned unknowns [u_n, v_n, u_s, v_s, p]
+    rows r0..r1.
     Inner solves: Jacobi / Chebyshev (the communication-avoiding schedule by default) or multigrid ("mg": one
     PartitionedMultigrid per inner inverse, ghost rows exchanged per operator, the coarse levels replicated).
 
@@ -1139,178 +1313,103 @@ class DistributedSchurPreconditioner(PlanProfiling):
                  device=None, layout="sell", f_mode="auto", pg_mode="auto", halo="auto", self_halo=False,
                  halo_overlap=False, ca="auto", fuse_g=True, mg_min_cells=1 << 14, mg_part_levels=None,
                  local_products=True, numerics="exact", kernel_opts=None):
-        for name, inner in (("inner_F", inner_F), ("inner_P", inner_P)):   # (before any torch.distributed call)
-            if getattr(inner, "accel", None) is not None:
-                raise ValueError(f"{name}: Chebyshev-accelerated multigrid (accel={inner.accel!r}) is not available on "
-                                 "the row-partitioned hierarchies; use accel=None here")
-            if getattr(inner, "coarsen", "even") != "even":
-                raise ValueError(f"{name}: coarsen={inner.coarsen!r} is not available under the row partition; use "
-                                 'coarsen="even" here')
+        _check_setup_args(inner_F, inner_P, halo, f_mode, pg_mode, ca, layout, numerics)
         import torch.distributed as dist
-        from .preconditioner import MultiphaseBlockPreconditioner
-        from .solve import InnerSolver, _check_numerics
-        self.numerics = _check_numerics(numerics)
+        self.numerics, self.layout = numerics, layout
         # this preconditioner's kernel choices (process defaults now + overrides): tolerance mode reads Gt_F_G's
         # symmetric half over the rank's row block (q13_sym, as one GPU); q13_mf is one-GPU only
         self.kernel_opts = _lib.kernel_opts(kernel_opts)
         # setup phase timings (MPBP_SETUP_TIMING=1: synchronise and stamp each phase; tools/setup_timing.py)
         self.setup_phases = {}
         _stamp = _phase_clock(self.setup_phases)
-        dev = torch.device(device or "cuda")
-        self.device = dev
-        world = dist.get_world_size(group)
-        rank = dist.get_rank(group)
-        # self_halo: a single rank still runs the partitioned apply, its ghost rows filled by the periodic
-        # self-exchange (exercises the interior / boundary launches and the halo path on one GPU)
-        self.part = part = RowPartition(n, world, rank, ghosts=bool(self_halo))
+        self.device = dev = torch.device(device or "cuda")
+        # the partition.  self_halo: a single rank still runs the partitioned apply, its ghost rows filled by the
+        # periodic self-exchange (exercises the interior / boundary launches and the halo path on one GPU)
+        world, backend = dist.get_world_size(group), dist.get_backend(group)
+        self.part = part = RowPartition(n, world, dist.get_rank(group), ghosts=bool(self_halo))
         self.partitioned = part.ghosts
-        if halo not in ("auto", "rccl", "torch"):
-            raise ValueError("halo must be 'auto', 'rccl' or 'torch'")
-        backend = dist.get_backend(group)
         self.halo_impl = halo if halo != "auto" else ("rccl" if backend == "nccl" else "torch")
-        bp = MultiphaseBlockPreconditioner(n, xi, eta_n, eta_s, device=dev)
-        rows_u = torch.from_numpy(part.owned_rows(N_VEL_FIELDS).astype(np.int32)).to(dev)
-        rows_p = torch.from_numpy(part.owned_rows(N_P_FIELDS).astype(np.int32)).to(dev)
+        red_dev = dev if backend == "nccl" else "cpu"   # where the setup's small all-reduces run
+        # the source of this rank's rows; multigrid inner solves form their levels from it too
         ik_f, ik_p = inner_F or InnerSolver(), inner_P or InnerSolver()
-        # the commutator products: only this rank's pressure rows of Gt_G and Gt_F_G (a product's row depends on that
-        # row of D alone: the same bits as the global product's row, for a 1 / world share of the SpGEMM work);
-        # multigrid inner solves form their levels from this rank's band of rows too (LocalHierarchy)
         self.local_products = bool(local_products) and world > 1
-        akw = dict(c=c, d_u=d_u)
-        Gs = None
-        if self.local_products:
-            # rank-local setup (preconditioner.py:299-341 row by row): F, D, G assembled on this rank's rows only
-            # (mpbp_stokes_*_rows, the global assembly's rows bit for bit), the products' right operands on the velocity
-            # rows a product row can reach -- grid rows within `sup` of the owned ones (the CA schedule's ghost depths
-            # included) -- in global row numbering; setup memory and work O(N / world + ghosts) instead of O(N)
-            st_F, st_D, st_G = bp.stencils(**akw)
-            F = bp.assemble_rows(_lib.OP_F, rows_u, **akw)
-            D = bp.assemble_rows(_lib.OP_D, rows_p, **akw)
-            G = bp.assemble_rows(_lib.OP_G, rows_u, **akw)
-            F.stencil, D.stencil, G.stencil = st_F, st_D, st_G
-            _stamp("assemble_owned_rows")
-            sweeps = lambda k: k.sweeps if k.kind in ("jacobi", "chebyshev") else 1   # noqa: E731
-            sup = min(n, sweeps(ik_f) + sweeps(ik_p) + 2)
-            grid_rows = np.unique(np.arange(part.r0 - sup, part.r1 + sup) % n) if part.L + 2 * sup < n \
-                else np.arange(n)
-            sup_u = np.sort(np.concatenate([f * part.N + (r * n + np.arange(n)) for f in range(N_VEL_FIELDS)
-                                            for r in grid_rows]))
-            sup_u = torch.from_numpy(sup_u.astype(np.int32)).to(dev)
-            Fs = bp.assemble_rows(_lib.OP_F, sup_u, global_shape=True, **akw)
-            Gs = bp.assemble_rows(_lib.OP_G, sup_u, global_shape=True, **akw)
-            _stamp("assemble_support_rows")
-            GtG, GtFG = bp.commutator_products(Fs, D, Gs)   # this rank's pressure rows, global columns
-            _stamp("commutator_products")
-            GtG.stencil = _gtg_stencil(D, G)
-            # tolerance mode: the two pressure grid rows above the owned block too (their products' rows, bit for bit
-            # the global product's), so the symmetric-half read has the lower slots of the first owned rows
-            q_rows = None
-            if self.numerics == "fast" and part.ghosts and part.L < n:
-                q_rows = GtFG
-                for k in (1, 2):   # (one grid row per assembly: the wrapped rows need not ascend)
-                    row = torch.from_numpy((((part.r0 - k) % n) * n + np.arange(n)).astype(np.int32)).to(dev)
-                    D1 = bp.assemble_rows(_lib.OP_D, row, **akw)
-                    q_rows = _csr_vstack(spgemm(spgemm(D1, Fs, alpha=-1.0), Gs, alpha=1.0), q_rows)
-                del D1
-            del Fs
-        else:
-            # (the preconditioner reads F, D and G alone: A's own CSR is not assembled to be dropped)
-            _, _, F, D, G = bp.get_big_A_matrix(matrix_free_A=n >= 3, **akw)
-            _stamp("assemble_global")
-            GtG, GtFG = bp.commutator_products(F, D, G)
-            _stamp("commutator_products")
-            q_rows = None
-            if self.numerics == "fast" and part.ghosts:   # grid rows r0 - 2 .. r0 + L - 1 of the global product
-                blk = np.concatenate([((part.r0 + k) % n) * n + np.arange(n) for k in range(-2, part.L)]).astype(np.int32)
-                q_rows = GtFG.extract(torch.from_numpy(blk).to(dev),
-                                      torch.arange(GtFG.shape[1], dtype=torch.int32, device=dev), GtFG.shape[1])
-        # Gt_F_G's diamond over the rank's row block, read from its symmetric upper half (k_q13p) when the product is
-        # symmetric to 1e-14 of its largest entry -- decided over all ranks, as one GPU decides over the whole grid
-        self.q13 = None
-        if q_rows is not None and n >= 5:
-            self.q13 = _q13_block(q_rows, n, part, group, dev if backend == "nccl" else "cpu")
-            if self.q13 is None or not self.q13[2]:
-                self.kernel_opts.q13_sym = 0
-        else:
-            self.kernel_opts.q13_sym = 0
-        del q_rows
-        lp = self.local_products
-        if f_mode not in ("auto", "stencil", "assembled"):
-            raise ValueError("f_mode must be 'auto', 'stencil' or 'assembled'")
-        if f_mode == "stencil" and F.stencil is None:
-            raise ValueError("f_mode='stencil' needs n >= 3")
-        self.f_stencil = F.stencil if f_mode in ("auto", "stencil") else None
-        self.pg_stencil = _pg_stencil(D, G, GtG, self.f_stencil, pg_mode)
-        # inner-solver bounds from the global operators: identical on every rank (rank-local: the Gershgorin bound is the
-        # maximum of the ranks' row bounds -- the same maximum, exactly)
-        def global_bound(M, rows):
-            t = torch.tensor([M.gershgorin(_row_diagonal(M, rows))], dtype=torch.float64,
-                             device=dev if backend == "nccl" else "cpu")
-            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
-            return float(t.item())
-        if lp and ik_f.kind == "chebyshev" and ik_f.lmax is None:
-            ik_f = InnerSolver("chebyshev", ik_f.sweeps, ik_f.lmin, global_bound(F, rows_u), ik_f.ratio)
-        self.inner_F = ik_f.resolve(F, None if lp else F.diagonal())
-        if self.local_products:
-            ip = ik_p
-            if ip.kind == "chebyshev" and ip.lmax is None:
-                ip = InnerSolver("chebyshev", ip.sweeps, ip.lmin, global_bound(GtG, rows_p), ip.ratio)
-            self.inner_P = ip.resolve(GtG, None)
-        else:
-            self.inner_P = (inner_P or InnerSolver()).resolve(GtG, GtG.diagonal())
+        src = (_RankLocalRows if self.local_products else _GlobalOperators)(
+            MultiphaseBlockPreconditioner(n, xi, eta_n, eta_s, device=dev), part, akw=dict(c=c, d_u=d_u),
+            inners=(ik_f, ik_p), want_q13=numerics == "fast" and part.ghosts, group=group, red_dev=red_dev,
+            mg_limits=(mg_min_cells, mg_part_levels), stamp=_stamp)
+        self._decide_q13(src.q13_rows(), group, red_dev)
+        self.f_stencil = _f_stencil(src.op["F"], f_mode)
+        self.pg_stencil = _pg_stencil(src.op["D"], src.op["G"], src.op["P"], self.f_stencil, pg_mode)
+        # inner-solver bounds from the global operators: identical on every rank
+        self.inner_F = src.resolve(ik_f, "F")
+        self.inner_P = src.resolve(ik_p, "P")
         mg_any = "mg" in (self.inner_F.kind, self.inner_P.kind)
         _stamp("inner_bounds")
-
-        def reach(M, rows, local=False):
-            sub = M if local else M.extract(rows, torch.arange(M.shape[1], dtype=torch.int32, device=dev), M.shape[1])
-            return halo_reach(sub.row_ptr, sub.col_idx, rows, n)
-
-        q = reach(GtFG, rows_p, lp)
-        self.h_u = max(1, reach(F, rows_u, lp), reach(D, rows_p, lp))
-        self.h_p = max(1, reach(G, rows_u, lp), reach(GtG, rows_p, lp), q)
-        # multigrid inner solves: the global hierarchies (every rank, setup only), split over the partition; level 0's
-        # ghost layout must also serve the restriction's reach
+        q = src.reach("Q")
+        self.h_u = max(1, src.reach("F"), src.reach("D"))
+        self.h_p = max(1, src.reach("G"), src.reach("P"), q)
+        # multigrid inner solves: the hierarchies split over the partition; level 0's ghost layout must also serve the
+        # restriction's reach
         self.mg_F = self.mg_P = None
-        if mg_any:
-            from .mg import FIELDS_PRESSURE, FIELDS_VELOCITY
-            if ca is True:
-                raise ValueError("ca=True needs Jacobi / Chebyshev inner solves (multigrid exchanges per operator)")
-            kw = dict(group=group, min_cells=mg_min_cells, max_part_levels=mg_part_levels)
-
-            def local_mg(ik, fields):
-                # this rank's band of level 0 (mg_bands), then its Galerkin levels (LocalHierarchy): no global operator
-                from .mg import level_sizes
-                sizes = level_sizes(n, ik.coarsest)
-                cap = mg_part_cap(sizes, part, len(fields), mg_min_cells, mg_part_levels)
-                S = mg_bands(sizes, fields, part, cap, dev)
-                _stamp("mg_bands")
-                if fields is FIELDS_VELOCITY:
-                    A0 = bp.assemble_rows(_lib.OP_F, S[0], **akw)
-                else:   # Gt_G's band rows = (-D) G on them, G on the velocity rows those rows of D reach
-                    Db = bp.assemble_rows(_lib.OP_D, S[0], **akw)
-                    Gb = bp.assemble_rows(_lib.OP_G, torch.unique(Db.col_idx), global_shape=True, **akw)
-                    A0 = spgemm(Db, Gb, alpha=-1.0)
-                    del Db, Gb
-                _stamp("mg_band_level0")
-                return LocalHierarchy(A0, S, sizes, fields, part, group, pre=ik.pre, post=ik.post,
-                                      cycles=int(ik.sweeps), ratio=ik.smooth_ratio, coarsest=ik.coarsest, stamp=_stamp)
-            if self.inner_F.kind == "mg":
-                gF = local_mg(self.inner_F, FIELDS_VELOCITY) if lp else \
-                    self.inner_F.multigrid(F, n, FIELDS_VELOCITY, F.diagonal())
-                self.mg_F = PartitionedMultigrid(gF, part, N_VEL_FIELDS, **kw) if self.partitioned else gF
-            if self.inner_P.kind == "mg":
-                gP = local_mg(self.inner_P, FIELDS_PRESSURE) if lp else \
-                    self.inner_P.multigrid(GtG, n, FIELDS_PRESSURE, GtG.diagonal())
-                self.mg_P = PartitionedMultigrid(gP, part, N_P_FIELDS, **kw) if self.partitioned else gP
-            if isinstance(self.mg_F, PartitionedMultigrid):
-                self.h_u = max(self.h_u, self.mg_F.h0)
-            if isinstance(self.mg_P, PartitionedMultigrid):
-                self.h_p = max(self.h_p, self.mg_P.h0)
+        kw = dict(group=group, min_cells=mg_min_cells, max_part_levels=mg_part_levels)
+        if self.inner_F.kind == "mg":
+            gF = src.hierarchy(self.inner_F, "F", FIELDS_VELOCITY)
+            self.mg_F = PartitionedMultigrid(gF, part, N_VEL_FIELDS, **kw) if self.partitioned else gF
+        if self.inner_P.kind == "mg":
+            gP = src.hierarchy(self.inner_P, "P", FIELDS_PRESSURE)
+            self.mg_P = PartitionedMultigrid(gP, part, N_P_FIELDS, **kw) if self.partitioned else gP
+        if isinstance(self.mg_F, PartitionedMultigrid):
+            self.h_u = max(self.h_u, self.mg_F.h0)
+        if isinstance(self.mg_P, PartitionedMultigrid):
+            self.h_p = max(self.h_p, self.mg_P.h0)
         _stamp("halo_reach_and_multigrid")
-        # communication-avoiding schedule (mpbp_schur_plan.ca): v's halo and x_b's halo only, deep enough for
-        # every matrix-free operator to also compute the ghost rows its successors read
-        if ca not in ("auto", True, False):
-            raise ValueError("ca must be 'auto', True or False")
+        self._ca_depths(ca, mg_any, q)
+        # CA schedule: the second F solve recomputes G x_p inside its sweeps from x_p's ghost rows (no G launch)
+        self.fuse_g = bool(fuse_g and self.ca and self.inner_F.kind == "chebyshev" and self.inner_F.sweeps >= 2)
+        if self.ca:   # diagonals on owned + ghost rows (the CA schedule's ghost-row sweeps stage x0)
+            self.diag_F_ext, self.diag_P_ext = (
+                src.ext_diagonal(key, torch.from_numpy(part.ext_rows(nf, h).astype(np.int32)).to(dev))
+                for key, nf, h in (("F", N_VEL_FIELDS, self.h_u), ("P", N_P_FIELDS, self.h_p)))
+        _stamp("ca_ghost_diagonals")
+        # the ext layout: every operator's owned rows, columns renumbered into owned + ghost slots
+        self.nu, self.np = part.n_owned(N_VEL_FIELDS), part.n_owned(N_P_FIELDS)
+        self.nu_ext, self.np_ext = part.n_ext(N_VEL_FIELDS, self.h_u), part.n_ext(N_P_FIELDS, self.h_p)
+        self.shape = (self.nu + self.np, self.nu + self.np)
+        ext = {"u": (torch.from_numpy(part.colmap(N_VEL_FIELDS, self.h_u)).to(dev), self.nu_ext),
+               "p": (torch.from_numpy(part.colmap(N_P_FIELDS, self.h_p)).to(dev), self.np_ext)}
+        for key, (attr, _, cols) in _OPS.items():
+            setattr(self, attr, src.owned_ext(key, *ext[cols]))
+        del src
+        torch.cuda.empty_cache()
+        self.diag_F = self.F.diagonal()
+        self.diag_P = self.GtG.diagonal()
+        _stamp("extract_ghost_layout")
+        own_cols = {"u": self.nu, "p": self.np}
+        self._sells, self._pieces = {}, {}
+        for key, (attr, _, cols) in _OPS.items():
+            self._sells[key], self._pieces[key] = _split_pieces(getattr(self, attr), own_cols[cols], layout, world > 1)
+        _stamp("sell_layouts")
+        self._workspace_and_halos(group, halo_overlap, _stamp)
+        _stamp("halo_and_workspace")
+        self._prof = None
+        self._plan = self._make_plan()
+        _stamp("plan")
+
+    def _decide_q13(self, q_rows, group, red_dev):
+        """Fast numerics: Gt_F_G's diamond over the rank's row block (self.q13), read from its symmetric upper half
+        (k_q13p; kernel option q13_sym) when the product is symmetric to 1e-14 of its largest entry -- decided over all
+        ranks, as one GPU decides over the whole grid.  q_rows: the source's q13_rows()."""
+        self.q13 = None
+        if q_rows is not None and self.part.n >= 5:
+            self.q13 = _q13_block(q_rows, self.part.n, self.part, group, red_dev)
+        if self.q13 is None or not self.q13[2]:
+            self.kernel_opts.q13_sym = 0
+
+    def _ca_depths(self, ca, mg_any: bool, q: int):
+        """The communication-avoiding schedule (mpbp_schur_plan.ca): v's halo and x_b's halo only, deep enough for
+        every matrix-free operator to also compute the ghost rows its successors read.  Sets ca and ca_q (Gt_F_G's
+        reach) and deepens h_u / h_p when the schedule is taken; ca=True raises where it cannot be."""
+        part = self.part
         self.ca, self.ca_q = False, q
         if ca and not mg_any and part.ghosts and self.f_stencil is not None and self.pg_stencil is not None:
             sf, sp = self.inner_F.sweeps - 1, self.inner_P.sweeps - 1
@@ -1322,166 +1421,56 @@ class DistributedSchurPreconditioner(PlanProfiling):
                 raise ValueError(f"ca=True needs {max(hu, hp)} grid rows per rank, the smallest has {part.min_rows}")
         elif ca is True:
             raise ValueError("ca=True needs a row partition and the matrix-free F, D, G, Gt_G")
-        # CA schedule: the second F solve recomputes G x_p inside its sweeps from x_p's ghost rows (no G launch)
-        self.fuse_g = bool(fuse_g and self.ca and self.inner_F.kind == "chebyshev" and self.inner_F.sweeps >= 2)
-        nu, np_ = part.n_owned(N_VEL_FIELDS), part.n_owned(N_P_FIELDS)
-        nu_ext, np_ext = part.n_ext(N_VEL_FIELDS, self.h_u), part.n_ext(N_P_FIELDS, self.h_p)
-        cm_u = torch.from_numpy(part.colmap(N_VEL_FIELDS, self.h_u)).to(dev)
-        cm_p = torch.from_numpy(part.colmap(N_P_FIELDS, self.h_p)).to(dev)
-        if self.ca:
-            gp_rows = torch.from_numpy(part.ext_rows(N_P_FIELDS, self.h_p).astype(np.int32)).to(dev)
-            if lp:   # F's diagonal on the owned + ghost velocity rows, from those rows alone
-                gu = torch.from_numpy(part.ext_rows(N_VEL_FIELDS, self.h_u).astype(np.int32)).to(dev)
-                self.diag_F_ext = _row_diagonal(bp.assemble_rows(_lib.OP_F, gu, **akw), gu)
-            else:
-                diag_F_glob = F.diagonal()
-            if lp:   # Gt_G's diagonal on the owned + ghost pressure rows, from those rows of the product alone
-                D_ext = bp.assemble_rows(_lib.OP_D, gp_rows, **akw)
-                self.diag_P_ext = _row_diagonal(spgemm(D_ext, Gs, alpha=-1.0), gp_rows)
-                del D_ext
-            else:
-                diag_P_glob = GtG.diagonal()
-        _stamp("ca_ghost_diagonals")
-        if lp:   # already this rank's rows, in owned order
-            own_u = torch.arange(rows_u.numel(), dtype=torch.int32, device=dev)
-            own_p = torch.arange(rows_p.numel(), dtype=torch.int32, device=dev)
-            self.F = F.extract(own_u, cm_u, nu_ext)
-            self.D = D.extract(own_p, cm_u, nu_ext)
-            self.G = G.extract(own_u, cm_p, np_ext)
-            self.GtG = GtG.extract(own_p, cm_p, np_ext)
-            self.GtFG = GtFG.extract(own_p, cm_p, np_ext)
-        else:
-            self.F = F.extract(rows_u, cm_u, nu_ext)
-            self.D = D.extract(rows_p, cm_u, nu_ext)
-            self.G = G.extract(rows_u, cm_p, np_ext)
-            self.GtG = GtG.extract(rows_p, cm_p, np_ext)
-            self.GtFG = GtFG.extract(rows_p, cm_p, np_ext)
-        del F, D, G, GtG, GtFG, Gs, bp
-        torch.cuda.empty_cache()
-        self.nu, self.np, self.nu_ext, self.np_ext = nu, np_, nu_ext, np_ext
-        self.shape = (nu + np_, nu + np_)
-        self.diag_F = self.F.diagonal()
-        self.diag_P = self.GtG.diagonal()
-        if self.ca and not lp:   # diagonals on owned + ghost rows (the CA schedule's ghost-row sweeps stage x0)
-            gu = torch.from_numpy(part.ext_rows(N_VEL_FIELDS, self.h_u)).to(dev)
-            self.diag_F_ext = diag_F_glob[gu].contiguous()
-            gp = torch.from_numpy(part.ext_rows(N_P_FIELDS, self.h_p)).to(dev)
-            self.diag_P_ext = diag_P_glob[gp].contiguous()
-            del diag_P_glob, diag_F_glob
 
-        _stamp("extract_ghost_layout")
-        mats = {"F": (self.F, nu), "D": (self.D, nu), "G": (self.G, np_), "P": (self.GtG, np_),
-                "Q": (self.GtFG, np_)}
-        self._pieces = {}
-        self.layout = layout
-        for key, (M, n_own_cols) in mats.items():
-            inner, bnd = boundary_ranges(M.row_ptr, M.col_idx, n_own_cols) if world > 1 else \
-                ([(0, M.shape[0])], [])
-            if layout == "sell":
-                S = M.to_sell(inner + bnd)
-                n_in = sum((b - a + 63) // 64 for a, b in inner)
-                self._pieces[key] = (S, S.sub(0, n_in), S.sub(n_in, S.nslices - n_in))
-            else:
-                self._pieces[key] = (M.plan_blocks(rows=inner) if inner else None,
-                                     M.plan_blocks(rows=bnd) if bnd else None)
-        _stamp("sell_layouts")
+    def _workspace_and_halos(self, group, halo_overlap: bool, stamp):
+        """The apply's work vectors (ext layout) and, under a partition, the exchanges of their ghost rows: the RCCL
+        halo object or the host-staged kinds, and each partitioned multigrid hierarchy built on them -- its level 0 is
+        the apply's own F / Gt_G with the apply's ping / pong buffers."""
+        part, dev = self.part, self.device
         f64 = dict(dtype=torch.float64, device=dev)
-        self._wu = [torch.zeros(nu_ext, **f64) for _ in range(4)]
-        self._wu_owned = torch.zeros(nu, **f64)
-        self._wp = [torch.zeros(np_ext, **f64) for _ in range(7)]
-        self._wu_ext = torch.zeros(nu_ext if self.ca else 0, **f64)
-        self._rccl = None
-        self._halos = None
-        if self.partitioned:
-            if self.halo_impl == "rccl":
-                self._rccl = RcclHalo(part, self.h_u, self.h_p, group, overlap=halo_overlap)
-            self._halos = _Halos(self.halo_impl, self._rccl, group, dev)
-            if self._rccl is None:
-                self._halos.add_kind(part, N_VEL_FIELDS, self.h_u, kind=_lib.VEC_VELOCITY)
-                self._halos.add_kind(part, N_P_FIELDS, self.h_p, kind=_lib.VEC_PRESSURE)
-            self._halos.register(*self._wu, *self._wp, *([self._wu_ext] if self.ca else []))
-            self._cb = self._halos.fn
-            # multigrid under the partition: level 0 is the apply's own F / Gt_G with its ping / pong buffers
-            if isinstance(self.mg_F, PartitionedMultigrid):
-                self.mg_F.build(self._halos, (self._wu[1], self._wu[2]), self.diag_F, self.h_u, kind0=_lib.VEC_VELOCITY)
-                _stamp("mg_build_F")
-            if isinstance(self.mg_P, PartitionedMultigrid):
-                self.mg_P.build(self._halos, (self._wp[4], self._wp[5]), self.diag_P, self.h_p, kind0=_lib.VEC_PRESSURE)
-                _stamp("mg_build_P")
-        else:
-            self._cb = _lib.HALO_FN()
-        _stamp("halo_and_workspace")
-        self._prof = None
-        self._plan = self._make_plan(world)
-        _stamp("plan")
+        self._wu = [torch.zeros(self.nu_ext, **f64) for _ in range(4)]
+        self._wu_owned = torch.zeros(self.nu, **f64)
+        self._wp = [torch.zeros(self.np_ext, **f64) for _ in range(7)]
+        self._wu_ext = torch.zeros(self.nu_ext if self.ca else 0, **f64)
+        self._rccl = self._halos = None
+        if not self.partitioned:
+            return
+        if self.halo_impl == "rccl":
+            self._rccl = RcclHalo(part, self.h_u, self.h_p, group, overlap=halo_overlap)
+        self._halos = _Halos(self.halo_impl, self._rccl, group, dev)
+        if self._rccl is None:
+            self._halos.add_kind(part, N_VEL_FIELDS, self.h_u, kind=_lib.VEC_VELOCITY)
+            self._halos.add_kind(part, N_P_FIELDS, self.h_p, kind=_lib.VEC_PRESSURE)
+        self._halos.register(*self._wu, *self._wp, *([self._wu_ext] if self.ca else []))
+        if isinstance(self.mg_F, PartitionedMultigrid):
+            self.mg_F.build(self._halos, (self._wu[1], self._wu[2]), self.diag_F, self.h_u, kind0=_lib.VEC_VELOCITY)
+            stamp("mg_build_F")
+        if isinstance(self.mg_P, PartitionedMultigrid):
+            self.mg_P.build(self._halos, (self._wp[4], self._wp[5]), self.diag_P, self.h_p, kind0=_lib.VEC_PRESSURE)
+            stamp("mg_build_P")
 
-    def _make_plan(self, world):
-        p = _lib.SchurPlan()
-        p.nu, p.np, p.nu_ext, p.np_ext = self.nu, self.np, self.nu_ext, self.np_ext
-        p.F, p.D, p.G = self.F.cstruct(), self.D.cstruct(), self.G.cstruct()
-        p.GtG, p.GtFG = self.GtG.cstruct(), self.GtFG.cstruct()
-        empty_b = _lib.RowBlocks(None, 0)
-        empty_s = _lib.Sell(0, 0, 0, 0, None, None, None, None)
-        p.use_sell = 1 if self.layout == "sell" else 0
-        for key in "FDGPQ":
-            piece = self._pieces[key]
-            if self.layout == "sell":
-                setattr(p, key + "s_int", piece[1].cstruct())
-                setattr(p, key + "s_bnd", piece[2].cstruct())
-                setattr(p, key + "_int", empty_b)
-                setattr(p, key + "_bnd", empty_b)
-            else:
-                setattr(p, key + "_int", piece[0].cstruct() if piece[0] else empty_b)
-                setattr(p, key + "_bnd", piece[1].cstruct() if piece[1] else empty_b)
-                setattr(p, key + "s_int", empty_s)
-                setattr(p, key + "s_bnd", empty_s)
-        p.diag_F, p.diag_P = self.diag_F.data_ptr(), self.diag_P.data_ptr()
-        p.inner_F, p.inner_P = self.inner_F.cstruct(), self.inner_P.cstruct()
-        for i, t in enumerate(self._wu):
-            p.wu[i] = t.data_ptr()
-        p.wu_owned = self._wu_owned.data_ptr()
-        for i, t in enumerate(self._wp):
-            p.wp[i] = t.data_ptr()
-        p.f_stencil = 1 if self.f_stencil is not None else 0
-        p.pg_stencil = 1 if self.pg_stencil is not None else 0
-        if self.f_stencil is not None:
-            st = self.f_stencil
-            p.f_prm = st.prm
-            p.f_cell, p.f_uface, p.f_vface = st.cell.data_ptr(), st.uface.data_ptr(), st.vface.data_ptr()
-        elif self.pg_stencil is not None:
-            p.f_prm, p.f_cell = self.pg_stencil.prm, self.pg_stencil.cell.data_ptr()
+    def _make_plan(self):
+        p = _fill_plan(self, self._pieces)
         # velocity (F, D) and pressure (G, Gt_G) input partitions of the stencil operators
         ghost = self.partitioned
         p.f_part = _lib.RowPart(self.part.r0, self.part.L, self.h_u if ghost else 0, 0)
         p.p_part = _lib.RowPart(self.part.r0, self.part.L, self.h_p if ghost else 0, 0)
-        p.halo = self._cb
+        p.halo = self._halos.fn if self._halos is not None else _lib.HALO_FN()
         p.halo_ctx = self._rccl.handle if self._rccl is not None else None
-        if self.mg_F is not None:
-            p.mg_F = ctypes.pointer(self.mg_F.cstruct())
-        if self.mg_P is not None:
-            p.mg_P = ctypes.pointer(self.mg_P.cstruct())
         # the in-order RCCL schedule gains nothing from splitting rows around the exchange: exchange first,
         # then one launch per sweep
         p.halo_first = 1 if (self._rccl is not None and not self._rccl.overlap) else 0
         p.ca, p.ca_reach_q = (1 if self.ca else 0), self.ca_q
-        if self.q13 is not None:
-            p.q13, p.q13_n = self.q13[1].data_ptr(), self.q13[0]
-        p.fuse_g = 1 if self.fuse_g else 0
-        p.f_numerics = _lib.NUMERICS_FAST if self.numerics == "fast" else _lib.NUMERICS_EXACT
-        p.opts = ctypes.pointer(self.kernel_opts)
         if self.ca:
             if self._rccl is not None and not self._rccl.overlap:   # v's two halves in one RCCL group
                 p.halo_pair = self._rccl.pair_fn
             p.wu_ext = self._wu_ext.data_ptr()
             p.diag_F_ext, p.diag_P_ext = self.diag_F_ext.data_ptr(), self.diag_P_ext.data_ptr()
-        p.prof_events = None
-        p.prof_capacity = 0
-        p.prof_count = ctypes.POINTER(ctypes.c_int32)()
         return p
 
     def sell_of(self, key):
         """The SELL-64 copy (interior + boundary slices) of F / D / G / P / Q, or None (CSR layout)."""
-        return self._pieces[key][0] if self.layout == "sell" else None
+        return self._sells[key]
 
     def apply(self, v: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         assert v.is_cuda and v.dtype == torch.float64 and v.numel() == self.nu + self.np

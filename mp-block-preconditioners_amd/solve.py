@@ -218,16 +218,92 @@ class PlanProfiling:
             for i in range(2 * cap):
                 lib().mpbp_event_destroy(evs[i])
         self._prof = None
-        self._plan.prof_events = None
-        self._plan.prof_capacity = 0
-        self._plan.prof_count = ctypes.POINTER(ctypes.c_int32)()
+        _no_profiling(self._plan)
+
+
+def _no_profiling(p):
+    """The plan's three profiling fields when no events are recorded."""
+    p.prof_events = None
+    p.prof_capacity = 0
+    p.prof_count = ctypes.POINTER(ctypes.c_int32)()
+
+
+def _fill_plan(pc, pieces):
+    """A new mpbp_schur_plan with everything the one-GPU and the row-partitioned preconditioner fill alike, read from
+    the attributes both carry; each _make_plan then adds what is its own.  pieces: F / D / G / P / Q -> ((interior,
+    boundary) row blocks, (interior, boundary) SELL slices), None where a piece is empty; the apply reads the kind
+    that pc.layout names.  One GPU is the partition with all rows interior and no ghost columns (nu_ext = nu)."""
+    p = _lib.SchurPlan()
+    p.nu, p.np = pc.nu, pc.np
+    p.nu_ext, p.np_ext = getattr(pc, "nu_ext", pc.nu), getattr(pc, "np_ext", pc.np)
+    p.F, p.D, p.G = pc.F.cstruct(), pc.D.cstruct(), pc.G.cstruct()
+    p.GtG, p.GtFG = pc.GtG.cstruct(), pc.GtFG.cstruct()
+    empty_b, empty_s = _lib.RowBlocks(None, 0), _lib.Sell(0, 0, 0, 0, None, None, None, None)
+    p.use_sell = 1 if pc.layout == "sell" else 0
+    for key in "FDGPQ":
+        blocks, sells = pieces[key]
+        for side, b, s in zip(("_int", "_bnd"), blocks, sells):
+            setattr(p, key + side, b.cstruct() if b is not None else empty_b)
+            setattr(p, key + "s" + side, s.cstruct() if s is not None else empty_s)
+    p.diag_F, p.diag_P = pc.diag_F.data_ptr(), pc.diag_P.data_ptr()
+    p.inner_F, p.inner_P = pc.inner_F.cstruct(), pc.inner_P.cstruct()
+    for i, t in enumerate(pc._wu):
+        p.wu[i] = t.data_ptr()
+    p.wu_owned = pc._wu_owned.data_ptr()
+    for i, t in enumerate(pc._wp):
+        p.wp[i] = t.data_ptr()
+    p.f_stencil = 1 if pc.f_stencil is not None else 0
+    p.pg_stencil = 1 if pc.pg_stencil is not None else 0
+    if pc.f_stencil is not None:
+        st = pc.f_stencil
+        p.f_prm = st.prm
+        p.f_cell, p.f_uface, p.f_vface = st.cell.data_ptr(), st.uface.data_ptr(), st.vface.data_ptr()
+    elif pc.pg_stencil is not None:
+        p.f_prm, p.f_cell = pc.pg_stencil.prm, pc.pg_stencil.cell.data_ptr()
+    if pc.q13 is not None:
+        p.q13, p.q13_n = pc.q13[1].data_ptr(), pc.q13[0]
+    if pc.mg_F is not None:
+        p.mg_F = ctypes.pointer(pc.mg_F.cstruct())
+    if pc.mg_P is not None:
+        p.mg_P = ctypes.pointer(pc.mg_P.cstruct())
+    p.fuse_g = 1 if pc.fuse_g else 0
+    p.f_numerics = _lib.NUMERICS_FAST if pc.numerics == "fast" else _lib.NUMERICS_EXACT
+    p.opts = ctypes.pointer(pc.kernel_opts)
+    _no_profiling(p)
+    return p
+
+
+def _check_f_mode(f_mode: str) -> str:
+    if f_mode not in ("auto", "stencil", "assembled"):
+        raise ValueError("f_mode must be 'auto', 'stencil' or 'assembled'")
+    return f_mode
+
+
+def _f_stencil(F, f_mode):
+    """F's FStencil when the F sweeps recompute its rows from thn (f_mode 'auto' on an F that carries one, 'stencil'),
+    else None: the stored F is streamed."""
+    st = getattr(F, "stencil", None)
+    if _check_f_mode(f_mode) == "stencil" and st is None:
+        raise ValueError("f_mode='stencil' needs n >= 3 (an F that carries its stencil: one GPU, F from "
+                         "MultiphaseBlockPreconditioner.get_big_A_matrix)")
+    return st if f_mode != "assembled" else None
+
+
+def _check_pg_mode(pg_mode: str) -> str:
+    if pg_mode not in ("auto", "stencil", "assembled"):
+        raise ValueError("pg_mode must be 'auto', 'stencil' or 'assembled'")
+    return pg_mode
+
+
+def _check_layout(layout: str) -> str:
+    if layout not in ("sell", "csr"):
+        raise ValueError("layout must be 'sell' or 'csr'")
+    return layout
 
 
 def _pg_stencil(D, G, GtG, f_stencil, pg_mode):
     """The PGStencil of Gt_G when D, G and Gt_G can run matrix-free (pg_mode 'auto' / 'stencil'), else None."""
-    if pg_mode not in ("auto", "stencil", "assembled"):
-        raise ValueError("pg_mode must be 'auto', 'stencil' or 'assembled'")
-    if pg_mode == "assembled":
+    if _check_pg_mode(pg_mode) == "assembled":
         return None
     sd, sg, sp = (getattr(M, "stencil", None) for M in (D, G, GtG))
     ok = all(isinstance(s, PGStencil) for s in (sd, sg, sp)) and \
@@ -339,18 +415,11 @@ class ApproxSchurPreconditioner(PlanProfiling, spla.LinearOperator):
         self._wu_owned = torch.empty(nu, **f64)
         self._wp = [torch.empty(np_, **f64) for _ in range(7)]
         self._prof = None
-        if layout not in ("sell", "csr"):
-            raise ValueError("layout must be 'sell' or 'csr'")
-        self.layout = layout
+        self.layout = _check_layout(layout)
         self._sell = [M.to_sell() for M in (self.F, self.D, self.G, self.GtG, self.GtFG)] if layout == "sell" else None
         # F sweeps: "stencil" recomputes F's rows from thn (bit-identical to the assembled F, ~4x fewer
         # HBM bytes); "assembled" streams the stored F; "auto" = stencil whenever F carries one.
-        if f_mode not in ("auto", "stencil", "assembled"):
-            raise ValueError("f_mode must be 'auto', 'stencil' or 'assembled'")
-        st = getattr(self.F, "stencil", None)
-        if f_mode == "stencil" and st is None:
-            raise ValueError("f_mode='stencil' needs F from MultiphaseBlockPreconditioner.get_big_A_matrix (n >= 3)")
-        self.f_stencil = st if f_mode in ("auto", "stencil") else None
+        self.f_stencil = _f_stencil(self.F, f_mode)
         # D, G, Gt_G likewise ("pg"): recomputed from the cell thn table when all three carry stencils of
         # one grid (get_big_A_matrix + commutator_products), else streamed from their stored copies.
         self.pg_stencil = _pg_stencil(self.D, self.G, self.GtG, self.f_stencil, pg_mode)
@@ -378,51 +447,10 @@ class ApproxSchurPreconditioner(PlanProfiling, spla.LinearOperator):
         super().__init__(dtype=np.float64, shape=(nu + np_, nu + np_))
 
     def _make_plan(self):
-        p = _lib.SchurPlan()
-        p.nu, p.np, p.nu_ext, p.np_ext = self.nu, self.np, self.nu, self.np
-        p.F, p.D, p.G = self.F.cstruct(), self.D.cstruct(), self.G.cstruct()
-        p.GtG, p.GtFG = self.GtG.cstruct(), self.GtFG.cstruct()
-        empty = _lib.RowBlocks(None, 0)
-        p.F_int, p.F_bnd = self.F.blocks.cstruct(), empty
-        p.D_int, p.D_bnd = self.D.blocks.cstruct(), empty
-        p.G_int, p.G_bnd = self.G.blocks.cstruct(), empty
-        p.P_int, p.P_bnd = self.GtG.blocks.cstruct(), empty
-        p.Q_int, p.Q_bnd = self.GtFG.blocks.cstruct(), empty
-        p.diag_F, p.diag_P = self.diag_F.data_ptr(), self.diag_P.data_ptr()
-        p.inner_F, p.inner_P = self.inner_F.cstruct(), self.inner_P.cstruct()
-        for i, t in enumerate(self._wu):
-            p.wu[i] = t.data_ptr()
-        p.wu_owned = self._wu_owned.data_ptr()
-        for i, t in enumerate(self._wp):
-            p.wp[i] = t.data_ptr()
-        p.use_sell = 1 if self._sell else 0
-        if self._sell:
-            esell = _lib.Sell(0, 0, 0, 0, None, None, None, None)
-            for name, S in zip(("Fs", "Ds", "Gs", "Ps", "Qs"), self._sell):
-                setattr(p, name + "_int", S.cstruct())
-                setattr(p, name + "_bnd", esell)
-        p.f_stencil = 1 if self.f_stencil is not None else 0
-        if self.f_stencil is not None:
-            p.f_prm = self.f_stencil.prm
-            p.f_cell, p.f_uface, p.f_vface = (t.data_ptr() for t in (self.f_stencil.cell, self.f_stencil.uface,
-                                                                    self.f_stencil.vface))
-        p.pg_stencil = 1 if self.pg_stencil is not None else 0
-        if self.pg_stencil is not None and self.f_stencil is None:
-            p.f_prm, p.f_cell = self.pg_stencil.prm, self.pg_stencil.cell.data_ptr()
-        p.halo = _lib.HALO_FN()
-        p.halo_ctx = None
-        p.prof_events = None
-        p.prof_capacity = 0
-        p.prof_count = ctypes.POINTER(ctypes.c_int32)()
-        if self.q13 is not None:
-            p.q13, p.q13_n = self.q13[1].data_ptr(), self.q13[0]
-        if self.mg_F is not None:
-            p.mg_F = ctypes.pointer(self.mg_F.cstruct())
-        if self.mg_P is not None:
-            p.mg_P = ctypes.pointer(self.mg_P.cstruct())
-        p.fuse_g = 1 if self.fuse_g else 0
-        p.f_numerics = _lib.NUMERICS_FAST if self.numerics == "fast" else _lib.NUMERICS_EXACT
-        p.opts = ctypes.pointer(self.kernel_opts)
+        # all rows interior, no boundary piece (the CSR row blocks are planned in the SELL layout too)
+        mats = (self.F, self.D, self.G, self.GtG, self.GtFG)
+        p = _fill_plan(self, {key: ((M.blocks, None), (S, None))
+                              for key, M, S in zip("FDGPQ", mats, self._sell or [None] * 5)})
         p.form = FORMS.index(self.form)   # MPBP_FORM_*
         return p
 

@@ -20,7 +20,8 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _worker(rank, world, port, n, layout, f_mode, kind, errfile, ca="auto", fuse_g=True, numerics="exact"):
+def _worker(rank, world, port, n, layout, f_mode, kind, errfile, ca="auto", fuse_g=True, numerics="exact",
+            local_products=True):
     try:
         os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         torch.cuda.set_device(0)
@@ -30,7 +31,8 @@ def _worker(rank, world, port, n, layout, f_mode, kind, errfile, ca="auto", fuse
         iF, iP = mpb.InnerSolver("chebyshev", 4), mpb.InnerSolver("chebyshev", 3)
         dpc = DistributedSchurPreconditioner(n, 1.0, 100.0, 1.0, inner_F=iF, inner_P=iP, layout=layout,
                                              f_mode=f_mode, ca=ca, fuse_g=fuse_g, numerics=numerics,
-                                             kernel_opts={"march_rows": kind})
+                                             local_products=local_products, kernel_opts={"march_rows": kind})
+        assert dpc.local_products == bool(local_products)
         assert dpc.fuse_g == bool(fuse_g and dpc.ca)
         assert (dpc.f_stencil is not None) == (f_mode != "assembled")
         if ca is True:
@@ -102,6 +104,15 @@ def test_distributed_fast_numerics_matches_single_gpu(world, n, ca, tmp_path):
     point as one GPU -- bit for bit."""
     errfile = str(tmp_path / "err.txt")
     _spawn(_worker, (world, _free_port(), n, "sell", "stencil", 4, errfile, ca, True, "fast"), world, errfile)
+
+
+@pytest.mark.parametrize("world,n,ca,numerics", [(2, 64, True, "exact"), (2, 64, True, "fast"), (3, 50, False, "exact")])
+def test_distributed_apply_global_products(world, n, ca, numerics, tmp_path):
+    """local_products=False at 2-3 ranks (bench.py --global-products): every rank assembles the global operators and
+    products and extracts its rows -- the CA schedule in both numerics and the per-sweep one, bit for bit against the
+    single-GPU apply like the rank-local setup."""
+    errfile = str(tmp_path / "err.txt")
+    _spawn(_worker, (world, _free_port(), n, "sell", "stencil", 4, errfile, ca, True, numerics, False), world, errfile)
 
 
 def _self_halo_worker(_index, port, n, halo, f_mode, pg_mode, kind, graph, errfile, overlap=False, ca="auto",
@@ -291,7 +302,7 @@ def _inner_pair(spec):
     return mpb.InnerSolver(kf, sf), mpb.InnerSolver(kp, sp)
 
 
-def _mg_worker(rank, world, port, n, inner, min_cells, halo, errfile, numerics="exact"):
+def _mg_worker(rank, world, port, n, inner, min_cells, halo, errfile, numerics="exact", local_products=True):
     """The partitioned Schur apply with multigrid inner solves vs the one-GPU apply with its default kernel choices
     (fast numerics at n >= 72: level 1 matrix-free in one launch on both sides -- k_gal1 / k_gal1p over the rank's owned
     coarse rows under the partition)."""
@@ -304,13 +315,16 @@ def _mg_worker(rank, world, port, n, inner, min_cells, halo, errfile, numerics="
                                                               PartitionedMultigrid)
         iF, iP = _inner_pair(inner)
         dpc = DistributedSchurPreconditioner(n, 1.0, 100.0, 1.0, inner_F=iF, inner_P=iP, halo=halo,
-                                             self_halo=(world == 1), mg_min_cells=min_cells, numerics=numerics)
+                                             self_halo=(world == 1), mg_min_cells=min_cells, numerics=numerics,
+                                             local_products=local_products)
         for m in (dpc.mg_F, dpc.mg_P):
             if m is not None:
                 assert isinstance(m, PartitionedMultigrid) and 1 <= m.part_levels <= m.g.nlevels - 1
                 if min_cells == 0 and world > 1:   # every level but the coarsest partitioned (where rows allow)
                     assert m.part_levels >= min(2, m.g.nlevels - 1), (m.part_levels, m.g.sizes)
-                if world > 1:   # rank-local levels: this rank's band of rows, no global operator
+                if world > 1 and not local_products:   # the global hierarchy, on every rank
+                    assert not isinstance(m.g, LocalHierarchy)
+                elif world > 1:   # rank-local levels: this rank's band of rows, no global operator
                     assert isinstance(m.g, LocalHierarchy)
                     if min_cells:
                         assert m.g.band[0].shape[0] < m.nf * m.g.sizes[0] ** 2, (m.g.band[0].shape, m.g.sizes)
@@ -365,6 +379,13 @@ def test_partitioned_multigrid_apply_matches_single_gpu(world, n, inner, min_cel
     coarse rows and ghost rows, or the replicated level when it is the gather level), below it both the stored level."""
     errfile = str(tmp_path / "err.txt")
     _spawn(_mg_worker, (world, _free_port(), n, inner, min_cells, halo, errfile, numerics), world, errfile)
+
+
+def test_partitioned_multigrid_global_products(tmp_path):
+    """local_products=False with multigrid inner solves: the global mg.Multigrid hierarchies of every rank split over
+    the partition (not a LocalHierarchy), bit for bit against the one-GPU apply."""
+    errfile = str(tmp_path / "err.txt")
+    _spawn(_mg_worker, (2, _free_port(), 64, MG1, 0, "auto", errfile, "exact", False), 2, errfile)
 
 
 def _fgmres_worker(rank, world, port, n, inner, maxiter, outdir, errfile, numerics="exact"):

@@ -111,3 +111,30 @@ def test_distributed_constructor_refuses_acceleration():
                dict(inner_P=mp.InnerSolver("mg", 3, accel="chebyshev", rho=0.1))):
         with pytest.raises(ValueError, match="row-partitioned"):
             DistributedSchurPreconditioner(16, 1.0, 100.0, 1.0, **kw)
+
+
+@pytest.mark.parametrize("arg", ["halo", "f_mode", "pg_mode", "ca", "layout", "numerics"])
+def test_distributed_constructor_checks_arguments_first(arg):
+    """Every refusal that depends on an argument alone is raised before any torch.distributed call (no process group
+    is initialised here; torch's own ValueError for that never reads "<argument> must be"): a bad argument on one rank
+    cannot leave the others waiting in a collective."""
+    import torch.distributed as dist
+    from mp_block_preconditioners_amd.distributed import DistributedSchurPreconditioner
+    assert not (dist.is_available() and dist.is_initialized())
+    with pytest.raises(ValueError, match=rf"^{arg} must be"):
+        DistributedSchurPreconditioner(16, 1.0, 100.0, 1.0, **{arg: "x"})
+
+
+def test_distributed_operators_check_halo_first():
+    """DistributedMatrix and DistributedStokesOperator refuse an unknown halo before any torch.distributed call."""
+    import torch.distributed as dist
+    from mp_block_preconditioners_amd import _lib
+    from mp_block_preconditioners_amd.distributed import DistributedMatrix, DistributedStokesOperator
+    from mp_block_preconditioners_amd.preconditioner import StokesOperator
+    assert not (dist.is_available() and dist.is_initialized())
+    with pytest.raises(ValueError, match=r"^halo must be"):
+        DistributedMatrix(None, 16, 5, halo="x")
+    prm = _lib.StokesParams()
+    prm.n = 16
+    with pytest.raises(ValueError, match=r"^halo must be"):
+        DistributedStokesOperator(StokesOperator(prm, (None, None, None)), halo="x")

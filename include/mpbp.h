@@ -198,6 +198,10 @@ typedef struct mpbp_mg_level {
     int32_t part_h;                  /* row partition: ghost rows each side of this level's x / t / r (0: whole level) */
     /* optional stencil-values copy of A (NULL: none; used for levels above the grouped kernel's row limit) */
     const mpbp_svl* A_svl;
+    /* the phase-coupled smoother's tables (mpbp_mg.smoother = MPBP_MG_SMOOTH_COUPLED; NULL: point Jacobi), nrows each:
+     * row i's line of the inverse of the 2 x 2 block that rows i and i +- nrows / 2 form (mpbp_cpl_blocks); lmin / lmax
+     * are then the interval of B^-1 A (mpbp_cpl_bound).  Unused on the coarsest level. */
+    const double *cpl_p, *cpl_q;
 } mpbp_mg_level;
 
 typedef void (*mpbp_halo_fn)(void* ctx, int32_t vec_kind, double* x_ext, int32_t phase, void* stream);
@@ -243,9 +247,28 @@ typedef struct mpbp_mg {
     int32_t accel;
     double accel_rho;                /* 0 < accel_rho < 1 */
     double* accel_x[2];
+    /* The smoother of every level but the coarsest (0: point Jacobi; zero-initialised structs behave as before).
+     * MPBP_MG_SMOOTH_COUPLED: point-block Jacobi over the two phases of a four-field velocity hierarchy -- Chebyshev
+     * on B^-1 A with B the 2 x 2 blocks of rows i and i + nrows / 2 (u_n, u_s of one face; v_n, v_s likewise), from
+     * the levels' cpl_p / cpl_q tables.  Each sweep is the level's residual launch and one mpbp_cpl_update launch; no
+     * fused point-Jacobi launch is taken and level 1 is the stored Galerkin level.  Robust at large drag, where
+     * diag(A)^-1 A has eigenvalues near 0 on oscillatory u_n = u_s modes.  Measured at 1024^2 (fast numerics, MI355X,
+     * DESIGN.md section 7): the apply costs 2.31 ms against 1.44 ms (mg:1 / mg:1); up to xi = 1e4 both smoothers
+     * contract alike (0.088) and point is faster, from xi = 1e6 the coupled V-cycle contracts by 0.10-0.14 where the
+     * point one reaches 0.43-0.90 and FGMRES with point stops converging.  The default stays point.  Refused (MPBP_ERR_ARG) with part_levels > 0,
+     * a smoothed level whose nrows is no multiple of 4, or missing tables. */
+    int32_t smoother;
+    /* Coupled smoother, level 0 the whole-grid matrix-free F of a Schur plan on one GPU: != 0 runs each sweep but the
+     * zero start as ONE launch -- the stencil kernel's cell-wise epilogue (the four rows of a cell sit in one lane,
+     * partners included) performs mpbp_cpl_update's operations on the row sums; exact numerics: the two-launch form's
+     * bits.  0: residual launch + mpbp_cpl_update.  Ignored where level 0 is a stored operator.  Measured at 1024^2:
+     * 2.31 against 2.36 ms per mg:1 / mg:1 apply, faster in each of 5 alternating rounds. */
+    int32_t cpl_fuse;
 } mpbp_mg;
 #define MPBP_MG_ACCEL_NONE 0
 #define MPBP_MG_ACCEL_CHEBYSHEV 1
+#define MPBP_MG_SMOOTH_POINT 0
+#define MPBP_MG_SMOOTH_COUPLED 1
 
 /* The apply's operands.  On one GPU every matrix's columns index the full vector and the
  * *_bnd row blocks are empty.  Under a row partition the columns index the "ext" layout of the
@@ -660,6 +683,27 @@ int mpbp_mg_accel_coeffs(double rho, int32_t K, double* omega, double* mu);
  * 16-byte aligned, else element-wise.  Graph-capturable. */
 int mpbp_mg_combine(int64_t n, const double* y, const double* xk, const double* xold, double omega, double mu,
                     const double* sub, double* out, void* stream);
+/* The phase-coupled smoother (mpbp_mg.smoother = MPBP_MG_SMOOTH_COUPLED).  A has nrows = 4 m rows (four stacked
+ * fields), H = nrows / 2, and row i's partner is pi(i) = i + H for i < H, else i - H.  With a = A[i,i], a' = A[pi,pi],
+ * k = A[i,pi], k' = A[pi,i] (an entry that is not stored reads as +0.0) and det = a a' - k k':
+ *   cpl_p[i] = a' / det,  cpl_q[i] = (-k) / det     (row i's line of the 2 x 2 block's inverse).
+ * A row without a stored diagonal, or whose det is not finite or <= 0, is MPBP_ERR_PATTERN and the message names the
+ * first such row.  Setup (syncs). */
+int mpbp_cpl_blocks(const mpbp_csr* A, double* cpl_p, double* cpl_q, void* stream);
+/* *lmax (host) = max_i sum_c |cpl_p[i] A[i,c] + cpl_q[i] A[pi(i),c]| = ||B^-1 A||_inf, a bound of the coupled
+ * smoother's spectrum: c runs over the union of the two rows' columns in ascending order (both rows must hold their
+ * columns ascending: else MPBP_ERR_PATTERN), an entry absent from one row contributes p (+0.0) resp. q (+0.0), the
+ * absolute values are added left to right from 0.0.  Setup (syncs). */
+int mpbp_cpl_bound(const mpbp_csr* A, const double* cpl_p, const double* cpl_q, double* lmax, void* stream);
+/* The coupled sweep's second launch, after r = b - A x (MPBP_SPMV_RESID), every operation rounded on its own:
+ *   z_i = cpl_p[i] r_i + cpl_q[i] r_pi(i);  d_i = c1 d_i + c2 z_i;  x_i = x_in_i + d_i;  x_out_i = x_i, or sub_i - x_i.
+ * x_in == NULL: the zero start, r is b and x_i = d_i = c2 z_i.  dzero != 0: d is read as +0.0 (a restart's first
+ * sweep).  store_d == 0: d is not written (a solve's last sweep).  One thread owns rows i and pi(i), so r is read
+ * once; 16-byte accesses when every pointer is 16-byte aligned.  nrows a multiple of 4; r must not alias x_out or d
+ * (x_out may be x_in).  Graph-capturable. */
+int mpbp_cpl_update(int32_t nrows, const double* cpl_p, const double* cpl_q, const double* r, const double* x_in,
+                    double c1, double c2, double* d, int32_t dzero, const double* sub, double* x_out, int32_t store_d,
+                    void* stream);
 
 /* ---- ghost rows over RCCL point-to-point (multi-GPU row partition) ------------------------------ */
 /* One RCCL group of neighbour sends / receives: the owned boundary rows (packed into one buffer per

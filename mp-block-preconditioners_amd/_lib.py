@@ -23,6 +23,7 @@ ASSOC_LEFT, ASSOC_RIGHT = 0, 1        # mpbp_triple_refill: (X Y) Z or X (Y Z)
 MG_CELL, MG_NODE = 0, 1
 MG_P, MG_R = 0, 1
 MG_ACCEL_NONE, MG_ACCEL_CHEBYSHEV = 0, 1   # mpbp_mg.accel
+MG_SMOOTH_POINT, MG_SMOOTH_COUPLED = 0, 1  # mpbp_mg.smoother
 HALO_BEGIN, HALO_END = 0, 1
 VEC_VELOCITY, VEC_PRESSURE = 0, 1
 PG_D, PG_G, PG_GTG = 0, 1, 2
@@ -74,7 +75,7 @@ class MgLevel(Structure):
                 ("R", Csr), ("R_blocks", RowBlocks), ("P", Csr), ("P_blocks", RowBlocks),
                 ("x", c_void_p), ("t", c_void_p), ("r", c_void_p), ("d", c_void_p), ("b", c_void_p),
                 ("A_sell", Sell), ("R_sell", Sell), ("P_sell", Sell), ("halo_kind", c_int32), ("part_h", c_int32),
-                ("A_svl", POINTER(Svl))]
+                ("A_svl", POINTER(Svl)), ("cpl_p", c_void_p), ("cpl_q", c_void_p)]
 
 
 HALO_FN = CFUNCTYPE(None, c_void_p, c_int32, c_void_p, c_int32, c_void_p)
@@ -146,7 +147,8 @@ class Mg(Structure):
                 ("part_levels", c_int32), ("gather_kind", c_int32), ("halo", HALO_FN), ("halo_ctx", c_void_p),
                 ("gather", GATHER_FN), ("tr_nfields", c_int32), ("tr_n0", c_int32), ("tr_ky", c_int32 * 8),
                 ("tr_kx", c_int32 * 8), ("opts", POINTER(KernelOpts)),
-                ("accel", c_int32), ("accel_rho", c_double), ("accel_x", c_void_p * 2)]
+                ("accel", c_int32), ("accel_rho", c_double), ("accel_x", c_void_p * 2),
+                ("smoother", c_int32), ("cpl_fuse", c_int32)]
 
 
 class SchurPlan(Structure):
@@ -276,6 +278,9 @@ _SIGNATURES = {
     "mpbp_mg_solve": ([POINTER(Mg), _P, _P, _P, _P], c_int),
     "mpbp_mg_accel_coeffs": ([c_double, c_int32, _P, _P], c_int),
     "mpbp_mg_combine": ([c_int64, _P, _P, _P, c_double, c_double, _P, _P, _P], c_int),
+    "mpbp_cpl_blocks": ([POINTER(Csr), _P, _P, _P], c_int),
+    "mpbp_cpl_bound": ([POINTER(Csr), _P, _P, POINTER(c_double), _P], c_int),
+    "mpbp_cpl_update": ([c_int32, _P, _P, _P, _P, c_double, c_double, _P, c_int32, _P, _P, c_int32, _P], c_int),
     "mpbp_gather": ([c_int32, _P, _P, _P, _P], c_int),
     "mpbp_scatter": ([c_int32, _P, _P, _P, _P], c_int),
     "mpbp_event_create": ([POINTER(c_void_p)], c_int),

@@ -124,6 +124,7 @@ int mg_solve(const mpbp_mg* m, const MgFine& fine, const double* b, double* x_ou
         return set_error(MPBP_ERR_ARG, "mg: hierarchy needs >= 2 levels, >= 1 cycle and the coarse inverse");
     if (x_out == fine.x || x_out == fine.t || x_out == fine.r || x_out == fine.d || b == x_out)
         return set_error(MPBP_ERR_ARG, "mg: x_out must not alias the level-0 work buffers or b");
+    if (int rc = mg_check_smoother(m)) return rc;
     if (m->accel) return mg_solve_accel(m, fine, b, x_out, sub, st);
     double* cur = fine.x;
     for (int k = 0; k < m->cycles; ++k) {

@@ -308,6 +308,7 @@ int mg_smooth(const OpPair& op, int32_t nrows, const double* diag, double lmin, 
 // interior / boundary rows and its halo; level 1 replicated whole or its owned rows), so both run the same level 1.
 bool mg_gal_ok(const mpbp_mg* m, const MgFine& f) {
     const OpRef& o = f.op.in;
+    if (m->smoother != MPBP_MG_SMOOTH_POINT) return false;   // a coupled level 1 is the stored Galerkin level
     if (!KO().mg_galerkin_mf || !o.stencil || !(o.sop == SOP_F || (o.sop == SOP_GTG && KO().mg_galerkin_mf_p)) ||
         o.stencil->f_numerics != MPBP_NUMERICS_FAST || m->nlevels <= 2 || !f.r || !f.d)
         return false;
@@ -323,6 +324,7 @@ bool mg_gal_ok(const mpbp_mg* m, const MgFine& f) {
 // wraps onto at most once (kernel option mg_fuse_l0).
 bool fpre_ok(const mpbp_mg* m, const MgFine& f) {
     const OpRef& o = f.op.in;
+    if (m->smoother != MPBP_MG_SMOOTH_POINT) return false;   // the fused descent smooths with point Jacobi
     if (!KO().mg_fuse_l0 || !o.stencil || o.sop != SOP_F || o.which != 0 || !f.op.bd.empty || f.halo || o.stencil->halo)
         return false;
     const mpbp_schur_plan* p = o.stencil;
@@ -355,6 +357,7 @@ int launch_fpre(const mpbp_schur_plan* p, const double* b, double lmin, double l
 // cell-centred transfers matrix-free, a grid the staging wraps onto at most once (kernel option mg_fuse_l0).
 bool gpre_ok(const mpbp_mg* m, const MgFine& f) {
     const OpRef& o = f.op.in;
+    if (m->smoother != MPBP_MG_SMOOTH_POINT) return false;
     if (!KO().mg_fuse_l0 || !o.stencil || o.sop != SOP_GTG || o.which != 0 || !f.op.bd.empty || f.halo || o.stencil->halo)
         return false;
     const mpbp_schur_plan* p = o.stencil;
@@ -406,6 +409,9 @@ int mg_vcycle(const mpbp_mg* m, int l, const MgFine& fine, const double* b, bool
               const double* sub, double** res, hipStream_t st) {
     const mpbp_mg_level& L = m->levels[l];
     const bool top = l == 0;
+    // the phase-coupled smoother (mg_coupled.inc): residual + k_cpl_update per sweep, none of the fused launches below
+    // (mg_gal_ok, fpre_ok and gpre_ok refuse it; k_grp_rr, residual + restriction only, and the transfers stay)
+    const bool cpl = m->smoother == MPBP_MG_SMOOTH_COUPLED;
     OpPair o = top ? fine.op : mg_level_op(L);
     MgGal gal{m, fine.op.in, fine.r, fine.d};   // (fine.r, fine.d: dead while level 1 runs)
     if (l == 1 && mg_gal_ok(m, fine)) {
@@ -440,7 +446,10 @@ int mg_vcycle(const mpbp_mg* m, int l, const MgFine& fine, const double* b, bool
         // an initial guess outside the level's two iterate buffers (the accelerated solve's x_k) is only read: the
         // pre-smoothing then ping-pongs between bx and bt, and everything after it works on those two
         double* spare = (!zero && xin != bx && xin != bt) ? bt : nullptr;
-        rc = mg_smooth(o, L.nrows, diag, L.lmin, L.lmax, L.pre, zero, b, &cur, alt, d, nullptr, nullptr, st, xch, 0, spare);
+        rc = cpl ? mg_smooth_cpl(o, L.nrows, L.cpl_p, L.cpl_q, L.lmin, L.lmax, L.pre, zero, b, &cur, alt, r, d, nullptr,
+                                 nullptr, st, xch, spare, top && m->cpl_fuse)
+                 : mg_smooth(o, L.nrows, diag, L.lmin, L.lmax, L.pre, zero, b, &cur, alt, d, nullptr, nullptr, st, xch, 0,
+                             spare);
         if (rc) return rc;
         alt = cur == bx ? bt : bx;
         if (small) {   // r = b - A x and b_c = R r in one launch (k_grp_rr)
@@ -521,7 +530,9 @@ int mg_vcycle(const mpbp_mg* m, int l, const MgFine& fine, const double* b, bool
     rc = use_mf_transfer(m, l) ? mg_transfer_mf(m, l, MPBP_MG_P, L.P.nrows, xc, EpiAdd{cur, cur}, st)
                                : mg_transfer(L.P, L.P_blocks, L.P_sell, MPBP_SPMV_ADD, xc, cur, cur, st);
     if (rc) return rc;
-    rc = mg_smooth(o, L.nrows, diag, L.lmin, L.lmax, L.post, false, b, &cur, alt, d, dst, sub, st, xch);
+    rc = cpl ? mg_smooth_cpl(o, L.nrows, L.cpl_p, L.cpl_q, L.lmin, L.lmax, L.post, false, b, &cur, alt, r, d, dst, sub,
+                             st, xch, nullptr, top && m->cpl_fuse)
+             : mg_smooth(o, L.nrows, diag, L.lmin, L.lmax, L.post, false, b, &cur, alt, d, dst, sub, st, xch);
     if (rc) return rc;
     *res = cur;
     return MPBP_OK;

@@ -1441,6 +1441,11 @@ template <bool S> struct RcpOk<EpiJacobiT<true, S, true>> : std::true_type {};
 template <bool S, bool D, bool B> struct RcpOk<EpiChebT<true, S, D, B, true>> : std::true_type {};
 template <bool S, bool D, bool B> struct RcpOk<EpiChebFirstT<true, S, D, B, true>> : std::true_type {};
 
+// A cell-wise epilogue (Epi::kCell; EpiCplChebT, mg_coupled.inc) finishes the NOUT rows of a cell together:
+// cell(rows, sums, x, pre) instead of one operator() per row.  k_march and k_direct take it by an if constexpr branch.
+template <class E, class = void> struct CellEpi : std::false_type {};
+template <class E> struct CellEpi<E, std::enable_if_t<E::kCell>> : std::true_type {};
+
 // XI entry xi * a * (1 - a) as the assembly evaluates it (left to right).
 __device__ inline double xi_of(double xi, double a) { return xi * a * (1.0 - a); }
 
@@ -2731,6 +2736,16 @@ k_march(S P, XS xs, int nchunks, Epi epi, BS bs = BS{}) {
             if constexpr (S::kFast) {   // tolerance mode: the cell's rows at once, reciprocal diagonals
                 double acc[NO], rd[NO];
                 P.rows4(gr, gc, ta, xa, cl, acc, rd);
+                if constexpr (CellEpi<Epi>::value) {   // (the reciprocal diagonals are not used)
+                    double xv[NO];
+                    int32_t rw[NO];
+#pragma unroll
+                    for (int o = 0; o < NO; ++o) {
+                        xv[o] = xa.X(o, gr, gc);
+                        rw[o] = P.out_row(o, lr, gc);
+                    }
+                    epi.cell(rw, acc, xv, pe);
+                } else {
 #pragma unroll
                 for (int o = 0; o < NO; ++o) {
                     set_diag(pe[o], rd[o]);
@@ -2738,10 +2753,24 @@ k_march(S P, XS xs, int nchunks, Epi epi, BS bs = BS{}) {
                     if constexpr (BS::on) set_b(pe[o], bs.b(o, gr, gc, gc, ta, bq));
                     epi(P.out_row(o, lr, gc), acc[o], pe[o]);
                 }
+                }
             } else {
             // the wrap-aware (sorting) form is exact for interior cells too: take it for the whole wave when
             // any of its cells is on the periodic edge, so a wave never runs both forms
             const bool edge = __builtin_amdgcn_readfirstlane(__any(gr == 0 || gr == n - 1 || gc == 0 || gc == n - 1)) != 0;
+            if constexpr (CellEpi<Epi>::value) {   // the cell's row sums (row<EDGE>'s bits), then the rows together
+                double acc[NO], xv[NO];
+                int32_t rw[NO];
+#pragma unroll
+                for (int o = 0; o < NO; ++o) {
+                    double dg;
+                    acc[o] = edge ? P.template row<true>(o, gr, gc, ta, xa, &dg, cl)
+                                  : P.template row<false>(o, gr, gc, ta, xa, &dg, cl);
+                    xv[o] = xa.X(S::NF == 1 ? 0 : o, gr, gc);
+                    rw[o] = P.out_row(o, lr, gc);
+                }
+                epi.cell(rw, acc, xv, pe);
+            } else {
 #pragma unroll
             for (int o = 0; o < NO; ++o) {
                 double dg;
@@ -2751,6 +2780,7 @@ k_march(S P, XS xs, int nchunks, Epi epi, BS bs = BS{}) {
                 set_x(pe[o], xa.X(S::NF == 1 ? 0 : o, gr, gc));
                 if constexpr (BS::on) set_b(pe[o], bs.b(o, gr, gc, gc, ta, bq));
                 epi(P.out_row(o, lr, gc), acc, pe[o]);
+            }
             }
             }
         }
@@ -2807,6 +2837,16 @@ __global__ void __launch_bounds__(256) k_direct(S P, XS xs, Epi epi, int la, int
         if (!live) return;
         double acc[NO], rd[NO];
         P.rows4(gr, gc, ta, xa, cl, acc, rd);
+        if constexpr (CellEpi<Epi>::value) {   // (the reciprocal diagonals are not used)
+            double xv[NO];
+            int32_t rw[NO];
+#pragma unroll
+            for (int o = 0; o < NO; ++o) {
+                xv[o] = xa.X(o, gr, gc);
+                rw[o] = P.out_row(o, lr, gc);
+            }
+            epi.cell(rw, acc, xv, pe);
+        } else {
 #pragma unroll
         for (int o = 0; o < NO; ++o) {
             set_diag(pe[o], rd[o]);
@@ -2814,8 +2854,10 @@ __global__ void __launch_bounds__(256) k_direct(S P, XS xs, Epi epi, int la, int
             if constexpr (BS::on) set_b(pe[o], bs.b(o, gr, gc, gc, ta, bq));
             epi(P.out_row(o, lr, gc), acc[o], pe[o]);
         }
+        }
         return;
     }
+    if constexpr (!CellEpi<Epi>::value) {   // (a cell-wise epilogue reaches k_direct through the tolerance-mode F rows only)
     const bool edge = __builtin_amdgcn_readfirstlane(__any(gr == 0 || gr == n - 1 || gc == 0 || gc == n - 1)) != 0;
     if (!live) return;
 #pragma unroll
@@ -2826,6 +2868,7 @@ __global__ void __launch_bounds__(256) k_direct(S P, XS xs, Epi epi, int la, int
         set_diag(pe[o], dg);
         set_x(pe[o], xa.X(S::NF == 1 ? 0 : o, gr, gc));
         epi(P.out_row(o, lr, gc), acc, pe[o]);
+    }
     }
 }
 
@@ -3303,6 +3346,7 @@ int launch_march_fixed(const S& P, const XS& xs, Epi epi, int rows_per_block, hi
 #include "abi_stencil.inc"
 #include "q13.inc"
 #include "schur_ops.inc"
+#include "mg_coupled.inc"
 #include "mg_solve.inc"
 #include "mg_accel.inc"
 #include "schur_inner.inc"

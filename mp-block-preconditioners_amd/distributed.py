@@ -725,6 +725,9 @@ class PartitionedMultigrid:
         if getattr(g, "coarsen", "even") != "even":
             raise ValueError(f"coarsen={g.coarsen!r} is not available under the row partition: the rows' halving and "
                              'ghost depths assume 2:1 transfers; use coarsen="even" here')
+        if getattr(g, "smoother", "point") != "point":
+            raise ValueError(f"smoother={g.smoother!r} is one GPU only: the row partition runs the point smoother "
+                             '(use smoother="point" here)')
         g = g if isinstance(g, LocalHierarchy) else _GlobalLevels(g)
         self.g, self.part0, self.nf, self.group = g, part, nfields, group
         dev = g.device
@@ -1272,6 +1275,9 @@ def _check_setup_args(inner_F, inner_P, halo, f_mode, pg_mode, ca, layout, numer
         if getattr(inner, "coarsen", "even") != "even":
             raise ValueError(f"{name}: coarsen={inner.coarsen!r} is not available under the row partition; use "
                              'coarsen="even" here')
+        if getattr(inner, "smoother", "point") != "point":
+            raise ValueError(f"{name}: smoother={inner.smoother!r} is one GPU only: the row-partitioned hierarchies "
+                             'run the point smoother; use smoother="point" here')
     _check_halo(halo)
     _check_f_mode(f_mode)
     _check_pg_mode(pg_mode)

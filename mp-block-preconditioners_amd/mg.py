@@ -9,7 +9,10 @@ that choice on the GPU:
 * transfers: per field, linear interpolation along each axis -- cell-centred (p; u along y; v along x)
   or node-centred (u along x, v along y) -- as CSR P, and R = P^T (``mpbp_mg_transfer_*``, exact values);
 * coarse operators: Galerkin A_{l+1} = R (A_l P) with the library's SpGEMM (every product kept);
-* smoother: Chebyshev-Jacobi on [lmax / ratio, lmax] with lmax the Gershgorin bound of diag(A)^-1 A;
+* smoother: Chebyshev-Jacobi on [lmax / ratio, lmax] with lmax the Gershgorin bound of diag(A)^-1 A (the default,
+  ``smoother="point"``); or, for the four velocity fields, ``smoother="coupled"``: Chebyshev on B^-1 A with B the 2 x 2
+  blocks that couple the two phases at each face (point-block Jacobi), lmax = ||B^-1 A||_inf -- robust at large drag,
+  where point Jacobi stops smoothing;
 * coarsest level: its dense pseudo-inverse (computed once on the host), applied by a dense kernel (one row per
   lane, the CSR row's order) from a column-major copy;
 * layouts: every level's operator and transfers also get a SELL-64 copy when their rows fit (< 256 entries):
@@ -39,6 +42,28 @@ FIELDS_PRESSURE = ((CELL, CELL),)
 
 
 COARSENINGS = ("even", "any")
+SMOOTHERS = ("point", "coupled")
+
+
+def _check_smoother(smoother: str):
+    if smoother not in SMOOTHERS:
+        raise ValueError(f"smoother must be one of {SMOOTHERS}, not {smoother!r}")
+
+
+def coupled_tables(A: DeviceCSR, out=None):
+    """(cpl_p, cpl_q) of the phase-coupled smoother (mpbp_cpl_blocks): row i's line a' / det, -k / det of the inverse of
+    the 2 x 2 block that rows i and i +- nrows / 2 form.  out: the pair of tensors to fill in place.  MpbpError naming
+    the first row without a stored diagonal or with a determinant that is not finite and positive."""
+    p, q = out if out is not None else (torch.empty(A.shape[0], dtype=torch.float64, device=A.device) for _ in range(2))
+    check(lib().mpbp_cpl_blocks(ctypes.byref(A.cstruct()), ptr(p), ptr(q), stream_handle()))
+    return p, q
+
+
+def coupled_bound(A: DeviceCSR, p: torch.Tensor, q: torch.Tensor) -> float:
+    """||B^-1 A||_inf with B the 2 x 2 phase blocks of coupled_tables (mpbp_cpl_bound): the coupled smoother's lmax."""
+    out = ctypes.c_double(0.0)
+    check(lib().mpbp_cpl_bound(ctypes.byref(A.cstruct()), ptr(p), ptr(q), ctypes.byref(out), stream_handle()))
+    return out.value
 
 
 def _check_coarsen(coarsen: str):
@@ -285,6 +310,13 @@ class Multigrid:
              neighbours (transfer(coarsen="any")); Galerkin rows below an odd level reach 86 entries, so the products
              and refresh take the wide forms (<= 128).  Odd-derived levels get no stencil-values copy and no fused
              residual-restriction kernel (their rows are ragged); everything else, accel included, is unchanged.
+    smoother "point" (default): Chebyshev-Jacobi on diag(A)^-1 A, today's code paths and bits.  "coupled": point-block
+             Jacobi over the two phases -- rows i and i + nrows / 2 (u_n, u_s at one face; v_n, v_s likewise) are
+             relaxed together through the inverse of their 2 x 2 block (coupled_tables), the interval's lmax is
+             ||B^-1 A||_inf (coupled_bound).  Four stacked fields only (FIELDS_VELOCITY); one GPU only.  Each sweep is
+             a residual launch and one mpbp_cpl_update launch: none of the fused point-Jacobi launches is taken, so
+             at drag xi = 1 (where both smoothers contract alike) it costs more than "point"; it is for xi h^2 >~ eta.
+    cpl_fuse smoother="coupled", level 0 the Schur apply's matrix-free F: one launch per sweep (set_coupled_fuse)
     rho      the contraction bound of one V-cycle; None: estimated here (and again by refresh) as ACCEL_RHO_MARGIN x
              the largest of contraction()'s last three ratios -- setup work that synchronises with the host
     """
@@ -292,9 +324,15 @@ class Multigrid:
     def __init__(self, A: DeviceCSR, n: int, fields=FIELDS_PRESSURE, pre: int = 2, post: int = 2, cycles: int = 1,
                  ratio: float = 4.0, coarsest: int = 8, diag: torch.Tensor | None = None, sell: bool = True,
                  fine_sell: bool = True, svl_min_rows: int | None | str = "default", kernel_opts: dict | None = None,
-                 accel: str | None = None, rho: float | None = None, coarsen: str = "even"):
+                 accel: str | None = None, rho: float | None = None, coarsen: str = "even",
+                 smoother: str = "point", cpl_fuse: bool = True):
         nf = len(fields)
         _check_coarsen(coarsen)
+        _check_smoother(smoother)
+        if smoother == "coupled" and nf != 4:
+            raise ValueError(f'smoother="coupled" pairs the two phases of the four velocity fields (FIELDS_VELOCITY): '
+                             f"this hierarchy has {nf} field{'s' if nf != 1 else ''}")
+        self.smoother = smoother
         if accel not in ACCELS:
             raise ValueError(f"accel must be one of {ACCELS}, not {accel!r}")
         if accel is not None and pre != post:
@@ -323,10 +361,14 @@ class Multigrid:
                              f"{nf * sizes[-1] ** 2} rows exceed the dense inverse's {MAX_COARSE_ROWS}{hint}")
         wide = coarsen == "any"   # Galerkin rows below an odd level reach 86 entries
         self.ops, self.diags, self.R, self.P, self.bounds, self.sizes = [], [], [], [], [], []
+        self.cpl = []   # smoother="coupled": per level (cpl_p, cpl_q), None on the coarsest (it is not smoothed)
         m = n
         while True:
+            last = _stop_coarsening(m, coarsest, len(self.ops) + 1, coarsen)
+            # (the coupled tables before the diagonal: their error names the row a missing diagonal sits in)
+            self.cpl.append(coupled_tables(A) if smoother == "coupled" and not last else None)
             d = diag if (not self.ops and diag is not None) else A.diagonal()
-            lmax = A.gershgorin(d)
+            lmax = coupled_bound(A, *self.cpl[-1]) if self.cpl[-1] is not None else A.gershgorin(d)
             self.ops.append(A)
             self.diags.append(d)
             self.bounds.append((lmax / ratio, lmax))
@@ -377,6 +419,8 @@ class Multigrid:
                 setattr(L, name, S.cstruct() if S is not None else _lib.Sell(0, 0, 0, 0, None, None, None, None))
             if self.svls[l] is not None:
                 L.A_svl = ctypes.pointer(self.svls[l].cstruct())
+            if self.cpl[l] is not None:
+                L.cpl_p, L.cpl_q = (t.data_ptr() for t in self.cpl[l])
         self._mg = _lib.Mg(len(self.ops), cycles, ctypes.cast(self._levels, ctypes.POINTER(_lib.MgLevel)),
                            self.coarse_inv.cstruct(), self.coarse_inv.blocks.cstruct(),
                            self.coarse_dense.data_ptr() if self.coarse_dense is not None else None)
@@ -384,6 +428,8 @@ class Multigrid:
         self.kernel_opts = _lib.kernel_opts(kernel_opts)
         self._mg.opts = ctypes.pointer(self.kernel_opts)
         set_transfer_kinds(self._mg, self.fields, n)
+        self._mg.smoother = _lib.MG_SMOOTH_COUPLED if smoother == "coupled" else _lib.MG_SMOOTH_POINT
+        self.set_coupled_fuse(cpl_fuse)
         # Chebyshev acceleration: x_k and x_{k-1} (the cycle's own buffers do not keep its initial guess), and rho
         self.accel = accel
         self.rho_estimated = accel is not None and rho is None
@@ -440,7 +486,7 @@ class Multigrid:
         """New values on the same grid: level 0's operator (the caller's) already holds them.  Recomputes, in place at
         every address the hierarchy's struct holds, each coarser operator (one fused R (A P) launch per level,
         mpbp_triple_refill -- its wide form under coarsen="any" --, no A P intermediate), every level's diagonal and
-        smoothing interval, the SELL and stencil-values copies and the coarsest pseudo-inverse -- what a fresh Multigrid over the same operator computes,
+        smoothing interval (the coupled smoother's tables too), the SELL and stencil-values copies and the coarsest pseudo-inverse -- what a fresh Multigrid over the same operator computes,
         bit for bit, with no structural work.  diag: level 0's new diagonal (default: recomputed; the tensor given to
         the constructor, refreshed by the caller, may be passed again).  timings: seconds per phase, each synchronised.
         An estimated acceleration rho is estimated again (phase "accel_rho"; an explicit one stays).
@@ -460,7 +506,11 @@ class Multigrid:
                         d.copy_(diag)
                 else:
                     d.copy_(A.diagonal())
-                lmax = A.gershgorin(d)
+                if self.cpl[l] is not None:   # the coupled tables in place, and their bound
+                    coupled_tables(A, out=self.cpl[l])
+                    lmax = coupled_bound(A, *self.cpl[l])
+                else:
+                    lmax = A.gershgorin(d)
                 self.bounds[l] = (lmax / self.ratio, lmax)
                 self._levels[l].lmin, self._levels[l].lmax = self.bounds[l]
         with timed_phase(timings, "layouts"):
@@ -480,6 +530,14 @@ class Multigrid:
             with timed_phase(timings, "accel_rho"):
                 self._rho = self.estimate_rho()
                 self._mg.accel_rho = self._rho
+
+    def set_coupled_fuse(self, on: bool):
+        """smoother="coupled" with level 0 the Schur apply's matrix-free F: each sweep as one launch (on, the default:
+        the stencil kernel's cell-wise epilogue; exact numerics give the same bits) or as the residual launch followed
+        by mpbp_cpl_update (off).  No effect on a stored level 0 or with the point smoother.  Graphs captured before
+        keep their launches: capture again."""
+        self.cpl_fuse = bool(on)
+        self._mg.cpl_fuse = 1 if (on and self.smoother == "coupled") else 0
 
     def set_matrix_free_transfers(self, on: bool):
         """Name (on) or hide (off) the field kinds in the hierarchy's struct: with them the whole-grid levels' transfers
@@ -505,4 +563,5 @@ class Multigrid:
     def __repr__(self):
         return (f"Multigrid(levels={self.sizes}, fields={len(self.fields)}, pre={self.pre}, post={self.post}, "
                 f"cycles={self.cycles}, ratio={self.ratio}" + (", coarsen='any'" if self.coarsen == "any" else "")
+                + (f", smoother={self.smoother!r}" if self.smoother != "point" else "")
                 + (f", accel={self.accel!r}, rho={self._rho:.4g}" if self.accel else "") + ")")

@@ -40,6 +40,9 @@ class InnerSolver:
            [lmax / smooth_ratio, lmax], coarsening stops at n <= coarsest
     coarsen  "mg" only: "even" halves while the grid size is even (n = m 2^k with a small odd m); "any" coarsens odd
            sizes too, by interpolated transfers, so any n >= 5 works (mg.Multigrid; one GPU only)
+    smoother "mg" only: "point" (default) is Chebyshev-Jacobi; "coupled" relaxes the two phases' unknowns at each face
+           together (point-block Jacobi, mg.Multigrid) -- for inner_F at large drag xi; the pressure hierarchy has one
+           field, so a coupled inner_P is refused; one GPU only
     accel, rho   "mg" only: accel="chebyshev" runs the `sweeps` V-cycles as a fixed Chebyshev semi-iteration (about 40x
            per cycle instead of 12x for F; needs pre == post and a nonsingular operator, so F, not Gt_G); rho is one
            cycle's contraction bound, None -> estimated at construction and on every refresh (mg.Multigrid)
@@ -56,9 +59,17 @@ class InnerSolver:
     accel: str | None = None
     rho: float | None = None
     coarsen: str = "even"
+    smoother: str = "point"
 
     def __post_init__(self):
         self._check_accel()
+        self._check_smoother()
+
+    def _check_smoother(self):
+        from .mg import _check_smoother
+        _check_smoother(self.smoother)
+        if self.smoother != "point" and self.kind != "mg":
+            raise ValueError(f"smoother={self.smoother!r} is a multigrid smoother: kind must be 'mg', not {self.kind!r}")
 
     def _check_accel(self):
         if self.accel is None and self.rho is None:
@@ -74,12 +85,13 @@ class InnerSolver:
 
     def resolve(self, M: DeviceCSR, diag: torch.Tensor) -> "InnerSolver":
         self._check_accel()
+        self._check_smoother()
         if self.kind == "jacobi":
             return InnerSolver("jacobi", int(self.sweeps), 0.0, 0.0, self.ratio)
         if self.kind == "mg":
             return InnerSolver("mg", int(self.sweeps), 0.0, 0.0, self.ratio, int(self.pre), int(self.post),
                                float(self.smooth_ratio), int(self.coarsest), self.accel,
-                               None if self.rho is None else float(self.rho), self.coarsen)
+                               None if self.rho is None else float(self.rho), self.coarsen, self.smoother)
         if self.kind != "chebyshev":
             raise ValueError(f"unknown inner solver {self.kind!r}")
         lmax = float(self.lmax) if self.lmax is not None else M.gershgorin(diag)
@@ -90,7 +102,7 @@ class InnerSolver:
         from .mg import Multigrid
         return Multigrid(M, n, fields, pre=self.pre, post=self.post, cycles=int(self.sweeps),
                          ratio=self.smooth_ratio, coarsest=self.coarsest, diag=diag, fine_sell=False,
-                         accel=self.accel, rho=self.rho, coarsen=self.coarsen)
+                         accel=self.accel, rho=self.rho, coarsen=self.coarsen, smoother=self.smoother)
 
     def cstruct(self):
         kind = {"chebyshev": _lib.INNER_CHEBYSHEV, "jacobi": _lib.INNER_JACOBI, "mg": _lib.INNER_MG}[self.kind]
@@ -399,6 +411,9 @@ class ApproxSchurPreconditioner(PlanProfiling, spla.LinearOperator):
         self.diag_P = self.GtG.diagonal()
         self.inner_F = (inner_F or InnerSolver()).resolve(self.F, self.diag_F)
         self.inner_P = (inner_P or InnerSolver()).resolve(self.GtG, self.diag_P)
+        if self.inner_P.smoother != "point":
+            raise ValueError(f"inner_P: smoother={self.inner_P.smoother!r} pairs the two phases of the velocity fields; "
+                             "the pressure hierarchy has one field (use it for inner_F)")
         # multigrid inner solves: hierarchies over F (4 velocity fields) and Gt_G (pressure) of the n x n grid
         self.mg_F = self.mg_P = None
         if "mg" in (self.inner_F.kind, self.inner_P.kind):
